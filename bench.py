@@ -25,18 +25,22 @@ the calibration samples (each rank folds nsamples/N samples into its Hessians), 
 (RCCL over xGMI), the factorization chain replicated, the rows of W split over the ranks, one all-gather of the packed
 rows + grids per group (gptq_amd.parallel.fasterquant_sharded).
 
-Besides the contract keys the JSON line carries
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps, writes the last timed step's
+outputs if --dump-outputs DIR is given, and prints the JSON line.  Besides the contract keys that line carries
   roofline      -- dominant kernel (the f16-MFMA Hessian SYRK, fp32 accumulate) at its dominant launch shape:
                    algorithmic flops (samples*S*C^2 per launch, the symmetric half) / measured launch time (HIP events
                    on the launching stream) against the 2.5 PFLOP/s dense f16 MFMA peak; `traffic` = HBM bytes per
                    launch from the PMC passes committed under profiles/ (same launch shape) or null;
+  phases        -- per-phase milliseconds and the solve-only Mparams/s (the scope the reference's own timer prints,
+                   gptq.py:139-293).
+With --full it also measures (each in runs of its own, after the timed steps)
   cpu_baseline  -- the oracle (reference algorithm, torch CPU fp32, pinned bit-for-bit to the reference by the golden
                    fixtures) timed on this box's host cores on a bounded sample of the same workload's shapes
                    (rank 0, N = 1 only);
-  phases        -- per-phase milliseconds and the solve-only Mparams/s (the scope the reference's own timer prints,
-                   gptq.py:139-293);
   also          -- the same measurement (fewer steps) on the other headline configuration (opt6.7b when the workload is
-                   llama7b), with the GPU / CPU ratio north_star's ">= 10x" refers to.
+                   llama7b), with the GPU / CPU ratio north_star's ">= 10x" refers to;
+  default_mode  -- the same block with the library's drop-in defaults (HESSIAN_DEFER = 1, no lazy Hessians);
+  end_to_end    -- gptq_amd.sequential.quantize_sequential on a 2-block Llama-7B-architecture model (llama7b, N = 1).
 """
 import argparse
 import json
@@ -110,6 +114,13 @@ def parse():
     ap.add_argument("--no-shared-inputs", action="store_true",
                     help="give q/k/v (gate/up) private calibration tensors (their Hessians are then accumulated per Linear)")
     ap.add_argument("--solve-streams", type=int, default=0, help="concurrent solves (0 = library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run the CPU baseline, the other headline configuration, the "
+                         "library-default mode and the end-to-end scope (a plain run measures the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (per Linear: packed qweight, scales, zeros) as "
+                         "DIR/<linear>.<array>.npy (float64 / float32); arrays over %d elements are stored as a fixed, "
+                         "seeded sample of their flattened values" % (1 << 18))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="skip the secondary measurement on the other headline config")
     ap.add_argument("--also-steps", type=int, default=2)
@@ -119,7 +130,7 @@ def parse():
     ap.add_argument("--end-to-end", type=int, default=-1, metavar="BLOCKS",
                     help="add `end_to_end`: gptq_amd.sequential.quantize_sequential on a random-init Llama-7B-architecture "
                          "model of BLOCKS decoder blocks (the reference's 'full quantization time' scope, opt.py:686-691); "
-                         "default: 2 blocks when the workload is llama7b on one GPU, 0 = off")
+                         "default: 2 blocks with --full when the workload is llama7b on one GPU, else 0 = off")
     ap.add_argument("--ppl-proxy", action="store_true",
                     help="add `ppl_proxy`: our OPT driver + evaluator vs the reference's numbers on the random-init OPT-125m "
                          "architecture of tests/golden/g6_opt125m.npz (a proxy: no Wiki2 / checkpoints offline)")
@@ -212,7 +223,9 @@ class Block:
                 e2.record()
                 # 3. pack
                 for (n, _, _, _), s in zip(g, solvers):
-                    out[n] = (G.pack_codes(s.codes, wl["bits"]), s.group_scale, s.group_zero)
+                    # without group tables the grids are the quantizer's per-row scale / zero (what callers read)
+                    grids = (s.group_scale, s.group_zero) if s.group_scale is not None else (s.quantizer.scale, s.quantizer.zero)
+                    out[n] = (G.pack_codes(s.codes, wl["bits"]),) + grids
                     s.free()
                 e3.record()
             marks.append((e0, e1, e2, e3))
@@ -229,8 +242,11 @@ class Block:
             self.step(False)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            self.step(True)
+        for i in range(steps):
+            out = self.step(True)
+            if i == steps - 1:
+                self.last_out = out          # what the timed path returned in its last step (--dump-outputs)
+            del out
         barrier()
         return time.perf_counter() - t0
 
@@ -350,15 +366,17 @@ def main():
         out["phases"]["solve_only_mparams_per_s"] = round(blk.params / (solve_ms / 1e3) / 1e6, 1) if solve_ms > 0 else None
         if world == 1 and args.project_gpus > 1:
             out["projection"] = projection(blk, args.project_gpus, blk.phase_ms["hessian"] / steps, dev)
+        if args.dump_outputs:
+            dump_outputs(blk.last_out, args.dump_outputs)
     del blk
     torch.cuda.empty_cache()
     if world == 1:
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.workload, WORKLOADS[args.workload], args.nsamples)
             out["cpu_baseline"] = cpu
         other = {"llama7b": "opt6.7b", "opt6.7b": "llama7b"}.get(args.workload)
-        if other and not args.no_also:
+        if args.full and other and not args.no_also:
             b2 = Block(other, args, dev, 0, 1)
             log(f"also: {other}, {args.also_steps} steps")
             el = b2.run(1, args.also_steps, barrier)
@@ -380,7 +398,7 @@ def main():
         if cpu is not None:
             out["gpu_over_cpu"] = {"whole_path": round(out["value"] / cpu["value"], 1),
                                    "solve_only": round(out["phases"]["solve_only_mparams_per_s"] / cpu["solve_only_mparams_per_s"], 1)}
-    if rank == 0 and world == 1 and not args.no_also:
+    if rank == 0 and world == 1 and args.full and not args.no_also:
         # the library's SAFE defaults (what a drop-in caller gets without opting in): add_batch launches its update before it
         # returns (HESSIAN_DEFER = 1) and every Linear folds its inputs as the hooks fire (no lazy Hessians)
         gmod.HESSIAN_DEFER, gmod.LAZY_HESSIANS = 1, False
@@ -394,7 +412,7 @@ def main():
         del b3
         torch.cuda.empty_cache()
         gmod.HESSIAN_DEFER, gmod.LAZY_HESSIANS = args.hessian_defer, not args.no_lazy_hessians
-    e2e_blocks = args.end_to_end if args.end_to_end >= 0 else (2 if (world == 1 and args.workload == "llama7b") else 0)
+    e2e_blocks = args.end_to_end if args.end_to_end >= 0 else (2 if (args.full and world == 1 and args.workload == "llama7b") else 0)
     if rank == 0 and world == 1 and e2e_blocks > 0:
         gmod.HESSIAN_DEFER = 1
         out["end_to_end"] = end_to_end(dev, e2e_blocks, args.nsamples, args.hessian_defer)
@@ -413,6 +431,35 @@ def main():
             real_stdout.write(json.dumps(out) + "\n")
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 18        # elements kept of a larger output array
+DUMP_LIMIT = 64 * 10**6      # bytes written by --dump-outputs in all
+
+
+def dump_outputs(outputs, dirname):
+    """{linear: (qweight int32, scale table, zero table)} of one step -> dirname/<linear>.<array>.npy.  Integer arrays are
+    written as float64 (exact), floating ones as float32.  An array of more than DUMP_SAMPLE elements is replaced by the
+    values at DUMP_SAMPLE flat positions drawn without replacement from a generator seeded by its name and shape, so
+    that two builds given the same arguments write the same positions."""
+    import zlib
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name in sorted(outputs):
+        for label, t in zip(("qweight", "scales", "zeros"), outputs[name]):
+            if t is None:
+                continue
+            a = t.detach().cpu().numpy()
+            a = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) and a.itemsize <= 4 else np.float64)
+            if a.size > DUMP_SAMPLE:
+                key = f"{name}.{label}:{'x'.join(map(str, a.shape))}"
+                rng = np.random.default_rng(zlib.crc32(key.encode()))
+                a = a.reshape(-1)[np.sort(rng.choice(a.size, DUMP_SAMPLE, replace=False))]
+            total += a.nbytes
+            assert total <= DUMP_LIMIT, f"--dump-outputs: more than {DUMP_LIMIT // 10**6} MB"
+            np.save(os.path.join(dirname, f"{name}.{label}.npy"), a)
+    log(f"outputs of the last timed step: {total / 2**20:.1f} MB in {dirname}")
 
 
 def projection(blk, n_gpus, hessian_ms, dev):

@@ -23,12 +23,35 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
+    """tests/golden/<name>.npz, or the same fixture kept in parts under 1 MiB each in tests/golden/<name>/: `_.npz` holds
+    the small arrays, `<key>.<i>.npz` the i-th slice of the flattened array <key> (slice 0 also holds its shape and
+    memory order)."""
+    path = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(path):
+        with np.load(path, allow_pickle=False) as z:
+            return {k: z[k] for k in z.files}
+    parts = os.path.join(GOLDEN, name)
+    with np.load(os.path.join(parts, "_.npz"), allow_pickle=False) as z:
+        out = {k: z[k] for k in z.files}
+    slices = {}
+    for f in os.listdir(parts):
+        if f != "_.npz":
+            key, i, _ = f.rsplit(".", 2)
+            slices.setdefault(key, {})[int(i)] = os.path.join(parts, f)
+    for key, files in slices.items():
+        flat, shape, order = [], None, "C"
+        for i in range(len(files)):
+            with np.load(files[i], allow_pickle=False) as z:
+                flat.append(z["a"])
+                if i == 0:
+                    shape, order = tuple(z["shape"]), "F" if bool(z["fortran"]) else "C"
+        out[key] = np.concatenate(flat).reshape(shape, order=order)
+    return out
 
 
 def golden_names(prefix):
-    return sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith(prefix) and f.endswith(".npz"))
+    return sorted(f[:-4] if f.endswith(".npz") else f for f in os.listdir(GOLDEN)
+                  if f.startswith(prefix) and (f.endswith(".npz") or os.path.isdir(os.path.join(GOLDEN, f))))
 
 
 @pytest.fixture(scope="session")
