@@ -52,6 +52,8 @@ _SIGNATURES = {
     "gptq_vecquant3matmul": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _i, _p]),
     "gptq_vecquant4matmul": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _i, _p]),
     "gptq_vecquant_matmul_grouped": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "gptq_quant_gemm": (C.c_int, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _z, _p]),
+    "gptq_quant_gemm_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

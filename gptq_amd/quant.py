@@ -141,6 +141,64 @@ def dequant_packed(qweight, scale, zero, bits, groupsize, dtype=torch.float16):
     return W
 
 
+def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_dtype=None):
+    """x [..., K] (fp16 / bf16) times the packed weights -> [..., N] in `out_dtype` (default x.dtype), through the
+    dequant GEMM of libgptq_hip.so (gptq_quant_gemm): the multi-token forward of the packed Linears.
+
+    qweight int32 [K/32*bits, N] (the modules' layouts); scales / zeros (zeros = zero*scale) hold N values for per-row
+    grids (groupsize <= 0) or [K/groupsize, N] for grouped ones; bias [N] or None.  fp32 accumulation, one rounding."""
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"quant_matmul: x must be fp16 or bf16, got {x.dtype}")
+    if out_dtype is None:
+        out_dtype = x.dtype
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"quant_matmul: out_dtype must be fp32, fp16 or bf16, got {out_dtype}")
+    bits, groupsize = int(bits), int(groupsize)
+    if bits not in (3, 4):
+        raise ValueError(f"quant_matmul: bits must be 3 or 4, got {bits}")
+    if qweight.dtype != torch.int32 or qweight.dim() != 2:
+        raise ValueError("quant_matmul: qweight must be an int32 [K/32*bits, N] tensor")
+    K, N = x.shape[-1], qweight.shape[1]
+    if K % 32 or qweight.shape[0] != K // 32 * bits:
+        raise ValueError(f"quant_matmul: x has {K} input features, qweight {tuple(qweight.shape)} implies "
+                         f"{qweight.shape[0] // bits * 32} (and K must be a multiple of 32)")
+    if groupsize > 0:
+        if groupsize % 32 or K % groupsize:
+            raise ValueError("quant_matmul: groupsize must be a multiple of 32 that divides K")
+        want = (K // groupsize, N)
+        if tuple(scales.shape) != want or tuple(zeros.shape) != want:
+            raise ValueError(f"quant_matmul: grouped scales / zeros must be {want}")
+    elif scales.numel() != N or zeros.numel() != N:
+        raise ValueError(f"quant_matmul: per-row scales / zeros must hold {N} values")
+    if bias is not None and bias.numel() != N:
+        raise ValueError(f"quant_matmul: bias must hold {N} values")
+    for name, t in (("x", x), ("qweight", qweight), ("scales", scales), ("zeros", zeros)):
+        _lib.require_gpu(t, name)
+    if bias is not None:
+        _lib.require_gpu(bias, "bias")
+    dev = x.device
+    outshape = list(x.shape[:-1]) + [N]
+    x2 = x.reshape(-1, K)
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    y = torch.empty((M, N), dtype=out_dtype, device=dev)
+    if M == 0:
+        return y.reshape(outshape)
+    qw = qweight.contiguous()
+    s = scales.to(torch.float32).contiguous()
+    z = zeros.to(torch.float32).contiguous()
+    b = bias.to(torch.float32).contiguous() if bias is not None else None
+    lib = _lib.load()
+    nbytes = lib.gptq_quant_gemm_workspace_bytes(M, K, N, bits, groupsize)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _lib.call("gptq_quant_gemm", _lib.ptr(x2), _lib.dtype_code(x2), x2.stride(0), M, _lib.ptr(qw), _lib.ptr(s),
+                  _lib.ptr(z), _lib.ptr(b), K, N, bits, groupsize, _lib.ptr(y), _lib.dtype_code(y), y.stride(0),
+                  _lib.ptr(ws), nbytes, _lib.stream(dev))
+    return y.reshape(outshape)
+
+
 class _QuantLinearBase(nn.Module):
     bits = 0
 
@@ -182,17 +240,22 @@ class _QuantLinearBase(nn.Module):
             self._matvec(x, y)
             y = y.to(dtype)
             return y.reshape(outshape)
+        if getattr(self, 'multi_token', False):
+            return quant_matmul(x, self.qweight, self.scales, self.zeros, self.bits, -1, self.bias)
         raise ValueError('Only supports a single token currently.')
 
 
 class Quant3Linear(_QuantLinearBase):
-    """3-bit packed Linear, single-token forward (reference quant.py:139-203)."""
+    """3-bit packed Linear (reference quant.py:139-203).  Single-token inputs take the mat-vec; with
+    `multi_token=True`, inputs of several tokens take the dequant GEMM (`quant_matmul`), otherwise they raise like
+    the reference."""
     bits = 3
 
-    def __init__(self, infeatures, outfeatures, faster=False):
+    def __init__(self, infeatures, outfeatures, faster=False, multi_token=False):
         super().__init__()
         self._alloc(infeatures, outfeatures)
         self.faster = faster
+        self.multi_token = multi_token   # inputs of several tokens -> quant_matmul (a plain attribute: no state_dict key)
 
     def _matvec(self, x, y):
         if self.faster:
@@ -210,9 +273,10 @@ class Quant4Linear(_QuantLinearBase):
     """
     bits = 4
 
-    def __init__(self, infeatures, outfeatures=None, zeros=None, faster=False):
+    def __init__(self, infeatures, outfeatures=None, zeros=None, faster=False, multi_token=False):
         super().__init__()
         self.faster = faster
+        self.multi_token = multi_token
         if isinstance(infeatures, nn.Module):
             linear, scales = infeatures, outfeatures
             self._alloc(linear.in_features, linear.out_features)
@@ -234,8 +298,9 @@ class QuantGroupLinear(nn.Module):
     object (`codes`, `group_scale`, `group_zero`); valid for static groups or runs without act-order.
     """
 
-    def __init__(self, bits, groupsize, infeatures, outfeatures):
+    def __init__(self, bits, groupsize, infeatures, outfeatures, multi_token=False):
         super().__init__()
+        self.multi_token = multi_token
         if bits not in (3, 4) or groupsize % 32 or infeatures % groupsize:
             raise ValueError("QuantGroupLinear: bits in {3,4}, groupsize % 32 == 0, in_features % groupsize == 0")
         self.bits, self.groupsize = bits, groupsize
@@ -245,7 +310,7 @@ class QuantGroupLinear(nn.Module):
         self.register_buffer('bias', torch.zeros(outfeatures))
 
     @classmethod
-    def from_gptq(cls, solver, bits):
+    def from_gptq(cls, solver, bits, multi_token=False):
         """Build from a `GPTQ` object after `fasterquant(groupsize=g, ...)`."""
         gs, gz = solver.group_scale, solver.group_zero          # [out, G]
         if gs is None:
@@ -253,7 +318,7 @@ class QuantGroupLinear(nn.Module):
         if solver.perm is not None and not getattr(solver, "static_groups", False):
             raise ValueError("QuantGroupLinear.from_gptq: act-order needs static groups for a g_idx-free format")
         n_out, n_in = solver.codes.shape
-        m = cls(bits, n_in // gs.shape[1], n_in, n_out)
+        m = cls(bits, n_in // gs.shape[1], n_in, n_out, multi_token=multi_token)
         m.qweight = pack_codes(solver.codes, bits)
         m.scales = gs.t().contiguous()
         m.zeros = (gz * gs).t().contiguous()
@@ -271,25 +336,38 @@ class QuantGroupLinear(nn.Module):
             quant_cuda.vecquant_matmul_grouped(xv.reshape(-1), self.qweight, y, self.scales, self.zeros,
                                                self.bits, self.groupsize)
             return y.to(dtype).reshape(outshape)
+        if self.multi_token:
+            return quant_matmul(x, self.qweight, self.scales, self.zeros, self.bits, self.groupsize, self.bias)
         raise ValueError('Only supports a single token currently.')
 
 
-def make_quant3(module, names, name='', faster=False):
+def make_quant3(module, names, name='', faster=False, multi_token=False):
     """Replace the named Linears by empty Quant3Linear modules (reference quant.py:205-216)."""
-    _make_quant(module, names, name, Quant3Linear, faster)
+    _make_quant(module, names, name, Quant3Linear, faster, multi_token)
 
 
-def make_quant4(module, names, name='', faster=False):
-    _make_quant(module, names, name, Quant4Linear, faster)
+def make_quant4(module, names, name='', faster=False, multi_token=False):
+    _make_quant(module, names, name, Quant4Linear, faster, multi_token)
 
 
-def _make_quant(module, names, name, cls, faster):
+def _make_quant(module, names, name, cls, faster, multi_token=False):
     if isinstance(module, _QuantLinearBase):
         return
     for attr in dir(module):
         tmp = getattr(module, attr)
         full = name + '.' + attr if name != '' else attr
         if full in names:
-            setattr(module, attr, cls(tmp.in_features, tmp.out_features, faster=faster))
+            setattr(module, attr, cls(tmp.in_features, tmp.out_features, faster=faster, multi_token=multi_token))
     for child_name, child in module.named_children():
-        _make_quant(child, names, name + '.' + child_name if name != '' else child_name, cls, faster)
+        _make_quant(child, names, name + '.' + child_name if name != '' else child_name, cls, faster, multi_token)
+
+
+def set_multi_token(model, enabled=True):
+    """Switch the multi-token forward (`quant_matmul`) of every packed Linear in `model` on or off, e.g. after
+    loading a checkpoint into a skeleton built without it.  Returns the number of modules switched."""
+    n = 0
+    for m in model.modules():
+        if isinstance(m, (_QuantLinearBase, QuantGroupLinear)):
+            m.multi_token = bool(enabled)
+            n += 1
+    return n

@@ -474,28 +474,29 @@ def _set_module(root, dotted, new):
     setattr(parent, parts[-1], new)
 
 
-def pack_model(model, quantizers, bits, faster=False):
+def pack_model(model, quantizers, bits, faster=False, multi_token=False):
     """Replace every quantized Linear by a packed module in place, like `opt_pack3` (opt.py:362-373).
 
     Per-row grids only (what `Quant3Linear` / `Quant4Linear` can hold): run the quantization with
     groupsize = -1.  The packing itself happens on the GPU (the reference loops over rows in numpy,
-    "TODO: perform packing on GPU", opt.py:361)."""
+    "TODO: perform packing on GPU", opt.py:361).  `multi_token=True` lets the packed model run inputs of several
+    tokens (prefill, `eval_ppl`) through the dequant GEMM."""
     from .quant import Quant3Linear, Quant4Linear
     cls = {3: Quant3Linear, 4: Quant4Linear}[bits]
     layers = find_layers(model)
     for name, q in quantizers.items():
         lin = layers[name]
-        packed = cls(lin.in_features, lin.out_features, faster=faster)
+        packed = cls(lin.in_features, lin.out_features, faster=faster, multi_token=multi_token)
         packed.pack(lin, q.scale.float(), q.zero.float())
         _set_module(model, name, packed)
     return model
 
 
-def make_packed_skeleton(model, names, bits, faster=False):
+def make_packed_skeleton(model, names, bits, faster=False, multi_token=False):
     """Empty packed modules for `names` (the load side of opt.py:375-402): load_state_dict then fills
     `qweight / scales / zeros / bias`."""
     from .quant import make_quant3, make_quant4
-    (make_quant3 if bits == 3 else make_quant4)(model, names, faster=faster)
+    (make_quant3 if bits == 3 else make_quant4)(model, names, faster=faster, multi_token=multi_token)
     return model
 
 

@@ -263,6 +263,21 @@ int gptq_vecquant_matmul_grouped(const void* vec, int vec_dtype, const int32_t* 
                                  const float* scales, const float* zeros, int height, int width,
                                  int bits, int groupsize, gptq_stream_t stream);
 
+/* Packed dequant GEMM -- the multi-token forward of the packed Linears (the reference's quant.py:188-197 only serves
+ * one token):
+ *   y[m][n] = sum_k x[m][k] * (scales[g][n]*q[k][n] - zeros[g][n]) (+ bias[n]),   g = k / groupsize
+ * x: [M, K] row-major, x_dtype GPTQ_F16 or GPTQ_BF16, leading dimension ldx >= K; qweight int32 [K/32*bits, N] in the
+ * layouts above (bits 3 or 4, K % 32 == 0); scales / zeros fp32 (zeros = zero*scale): [N] when groupsize <= 0, else
+ * [K/groupsize, N] with groupsize % 32 == 0 and K % groupsize == 0; bias fp32 [N] or NULL; y: [M, N], y_dtype GPTQ_F32,
+ * GPTQ_F16 or GPTQ_BF16, leading dimension ldy >= N.  fp32 accumulation on the exact integer codes, the grid applied per
+ * group as scale*sum(q*x) - zero*sum(x), bias added in fp32, one rounding to y_dtype.  workspace: at least
+ * gptq_quant_gemm_workspace_bytes(M, K, N, bits, groupsize) bytes (0 for shapes that need none; the query needs no
+ * device).  Deterministic: the same call gives bit-identical y. */
+int gptq_quant_gemm(const void* x, int x_dtype, int ldx, int M, const int32_t* qweight, const float* scales,
+                    const float* zeros, const float* bias, int K, int N, int bits, int groupsize, void* y, int y_dtype,
+                    int ldy, void* workspace, size_t workspace_bytes, gptq_stream_t stream);
+size_t gptq_quant_gemm_workspace_bytes(int M, int K, int N, int bits, int groupsize);
+
 #ifdef __cplusplus
 }
 #endif
