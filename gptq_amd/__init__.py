@@ -6,6 +6,6 @@ call does, and fails loudly if the library was not built (`python -m gptq_amd.bu
 from .gptq import GPTQ, fasterquant_many, flush_pending  # noqa: F401
 from .modelutils import DEV, find_layers  # noqa: F401
 from .quant import (Quant3Linear, Quant4Linear, QuantGroupLinear, Quantizer, make_quant3,  # noqa: F401
-                    make_quant4, pack_codes, quant_matmul, quantize, set_multi_token)
+                    make_quant4, pack_codes, pack_grouped, quant_matmul, quantize, set_multi_token)
 
 __version__ = "0.1.0"

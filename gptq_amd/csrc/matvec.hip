@@ -46,15 +46,24 @@ template <typename TV> __device__ __forceinline__ float mv_to_f32(TV v);
 template <> __device__ __forceinline__ float mv_to_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ float mv_to_f32<__half>(__half v) { return __half2float(v); }
 
+// Element k of the staged x chunk: vec[k], or with PERM (act-order storage) vec[perm[k]]; an index outside the n_in
+// inputs stages 0 (never a stray read).
+template <typename TV, bool PERM>
+__device__ __forceinline__ float mv_stage(const TV* __restrict__ vec, const int32_t* __restrict__ perm, long k, int n_in) {
+  if (!PERM) return mv_to_f32<TV>(vec[k]);
+  const int i = perm[k];
+  return (unsigned)i < (unsigned)n_in ? mv_to_f32<TV>(vec[i]) : 0.f;
+}
+
 // VW = output columns per thread (4: 16-byte loads; 1: fallback for width % 4 != 0)
 // groupsize == 0: one (scale, zero) per output column ([width]), applied once per workgroup.
 // groupsize  > 0: grouped grids, tables [in/groupsize, width] (row = group), applied per 32-input group:
 //                 y += s[g][col] * sum_{k in group}(q x) - z[g][col] * sum_{k in group}(x)   (SURVEY row f4).
-template <int BITS, int VW, typename TV, bool GROUPED>
+template <int BITS, int VW, typename TV, bool GROUPED, bool PERM = false>
 __global__ __launch_bounds__(256) void matvec_kernel(const TV* __restrict__ vec, const int32_t* __restrict__ mat,
                                                      float* __restrict__ mul, const float* __restrict__ scales,
                                                      const float* __restrict__ zeros, int ngroups, int width,
-                                                     int kgroups, int groupsize) {
+                                                     int kgroups, int groupsize, const int32_t* __restrict__ perm = nullptr) {
   __shared__ __attribute__((aligned(16))) float xs[MV_KGROUPS_MAX * 32];
   __shared__ float xs32[MV_KGROUPS_MAX];
   __shared__ float red[4][64 * VW + 1];
@@ -67,7 +76,7 @@ __global__ __launch_bounds__(256) void matvec_kernel(const TV* __restrict__ vec,
   // stage the x chunk (fp32) and its sum
   float part = 0.f;
   for (int k = tid; k < kgroups * 32; k += 256) {
-    const float v = (k < ng * 32) ? mv_to_f32<TV>(vec[(long)g0 * 32 + k]) : 0.f;
+    const float v = (k < ng * 32) ? mv_stage<TV, PERM>(vec, perm, (long)g0 * 32 + k, ngroups * 32) : 0.f;
     xs[k] = v;
     part += v;
   }
@@ -252,11 +261,13 @@ constexpr int MV_PF = 2;
 constexpr int MV2_KG_MAX = 128;
 static inline size_t matvec2_lds_bytes(int kg) { return sizeof(float) * ((size_t)kg * (32 + 32 + 2) + 4 * 257); }
 
-template <int BITS, typename TV, bool GROUPED, int ABL = 0>   // ABL: timing-only diagnostic builds (results are wrong)
+// PERM: act-order storage, packed row k multiplies vec[perm[k]]: the gather happens here, while x is staged, so the pair
+// table, the decode and the accumulation below are those of the plain kernel.
+template <int BITS, typename TV, bool GROUPED, int ABL = 0, bool PERM = false>   // ABL: timing-only diagnostic builds (results are wrong)
 __global__ __launch_bounds__(256) void matvec2_kernel(const TV* __restrict__ vec, const int32_t* __restrict__ mat,
                                                       float* __restrict__ mul, const float* __restrict__ scales,
                                                       const float* __restrict__ zeros, int ngroups, int width,
-                                                      int groupsize, int KG) {
+                                                      int groupsize, int KG, const int32_t* __restrict__ perm = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float mv_lds[];
   float* XP = mv_lds;                                     // [KG][16][2] activations of the pair slots, times 2^-p
   float* xs = XP + KG * 32;                               // [KG][32] the x chunk in stream order
@@ -287,7 +298,8 @@ __global__ __launch_bounds__(256) void matvec2_kernel(const TV* __restrict__ vec
   }
 
   // ---- stage x in fp32, then the pre-scaled pair table ----
-  for (int k = tid; k < KG * 32; k += 256) xs[k] = (k < ng * 32) ? mv_to_f32<TV>(vec[(long)g0 * 32 + k]) : 0.f;
+  for (int k = tid; k < KG * 32; k += 256)
+    xs[k] = (k < ng * 32) ? mv_stage<TV, PERM>(vec, perm, (long)g0 * 32 + k, ngroups * 32) : 0.f;
   __syncthreads();
   {
     const int t = tid & 15;
@@ -360,7 +372,8 @@ __global__ __launch_bounds__(256) void matvec2_kernel(const TV* __restrict__ vec
 
 template <int BITS>
 static int launch_matvec(const void* vec, int vec_dtype, const int32_t* mat, float* mul, const float* scales,
-                         const float* zeros, int height, int width, int groupsize, hipStream_t s, const char* who) {
+                         const float* zeros, int height, int width, int groupsize, hipStream_t s, const char* who,
+                         const int32_t* perm = nullptr) {
   GPTQ_CHECK_ARG(groupsize == 0 || (groupsize > 0 && groupsize % 32 == 0), "%s: groupsize must be a multiple of 32", who);
   GPTQ_CHECK_ARG(vec && mat && mul && scales && zeros, "%s: null pointer", who);
   GPTQ_CHECK_ARG(height > 0 && width > 0 && height % BITS == 0, "%s: height must be a positive multiple of %d", who, BITS);
@@ -393,7 +406,10 @@ static int launch_matvec(const void* vec, int vec_dtype, const int32_t* mat, flo
 #endif
 #define MV2_LAUNCH(TV)                                                                                             \
   do {                                                                                                             \
-    if (groupsize > 0)                                                                                             \
+    if (groupsize > 0 && perm)                                                                                     \
+      matvec2_kernel<BITS, TV, true, 0, true><<<grid2, 256, lds, s>>>(static_cast<const TV*>(vec), mat, mul, scales, \
+                                                                      zeros, ngroups, width, groupsize, kg, perm);   \
+    else if (groupsize > 0)                                                                                        \
       matvec2_kernel<BITS, TV, true><<<grid2, 256, lds, s>>>(static_cast<const TV*>(vec), mat, mul, scales, zeros, \
                                                              ngroups, width, groupsize, kg);                       \
     else                                                                                                           \
@@ -411,7 +427,10 @@ static int launch_matvec(const void* vec, int vec_dtype, const int32_t* mat, flo
   GPTQ_CHECK_ARG(grid.y <= 65535, "%s: too many input groups", who);
 #define MV_LAUNCH(VW, TV)                                                                                          \
   do {                                                                                                             \
-    if (groupsize > 0)                                                                                             \
+    if (groupsize > 0 && perm)                                                                                     \
+      matvec_kernel<BITS, VW, TV, true, true><<<grid, 256, 0, s>>>(static_cast<const TV*>(vec), mat, mul, scales,    \
+                                                                   zeros, ngroups, width, kgroups, groupsize, perm); \
+    else if (groupsize > 0)                                                                                        \
       matvec_kernel<BITS, VW, TV, true><<<grid, 256, 0, s>>>(static_cast<const TV*>(vec), mat, mul, scales, zeros, \
                                                              ngroups, width, kgroups, groupsize);                  \
     else                                                                                                           \
@@ -455,4 +474,18 @@ extern "C" int gptq_vecquant_matmul_grouped(const void* vec, int vec_dtype, cons
                             static_cast<hipStream_t>(stream), "gptq_vecquant_matmul_grouped");
   return launch_matvec<4>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
                           static_cast<hipStream_t>(stream), "gptq_vecquant_matmul_grouped");
+}
+
+extern "C" int gptq_vecquant_matmul_grouped_perm(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
+                                                 const float* scales, const float* zeros, const int32_t* perm,
+                                                 int height, int width, int bits, int groupsize, gptq_stream_t stream) {
+  const char* who = "gptq_vecquant_matmul_grouped_perm";
+  GPTQ_CHECK_ARG(bits == 3 || bits == 4, "%s: bits must be 3 or 4", who);
+  GPTQ_CHECK_ARG(groupsize > 0, "%s: groupsize must be positive", who);
+  GPTQ_CHECK_ARG((height / bits * 32) % groupsize == 0, "%s: in_features must be a multiple of groupsize", who);
+  if (bits == 3)
+    return launch_matvec<3>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
+                            static_cast<hipStream_t>(stream), who, perm);
+  return launch_matvec<4>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
+                          static_cast<hipStream_t>(stream), who, perm);
 }

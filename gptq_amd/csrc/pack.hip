@@ -162,13 +162,75 @@ static int launch_pack(const T* src, int ld, int n_out, int n_in, const float* s
   return GPTQ_OK;
 }
 
+// Grouped pack from weights: storage column j of row o holds the code of input perm[j] (perm == nullptr: j), on the grid
+// of group j / groupsize: code = clamp(round((w + zeros[g][o]) / scales[g][o]), 0, maxq), tables [G, out] (zeros =
+// zero*scale), i.e. quant.py:158 per group plus the clamp of quant.py:9.  Same tiles and pack phase as pack_kernel;
+// a thread's 4 storage columns lie in one 32-group, hence in one group of the grid.
+template <typename T, int BITS>
+__global__ __launch_bounds__(256) void pack_grouped_kernel(const T* __restrict__ src, int lds_, int n_out, int n_in,
+                                                           const float* __restrict__ scales,
+                                                           const float* __restrict__ zeros, int groupsize,
+                                                           const int32_t* __restrict__ perm,
+                                                           int32_t* __restrict__ qweight) {
+  __shared__ uint32_t cs[PT_O][PT_I + 1];
+  const int tid = threadIdx.x;
+  const int o0 = blockIdx.y * PT_O, i0 = blockIdx.x * PT_I;
+  const float maxq = (float)((1 << BITS) - 1);
+  const int il = (tid & 31) * 4;
+#pragma unroll
+  for (int pass = 0; pass < PT_O / 8; ++pass) {
+    const int ol = pass * 8 + (tid >> 5);
+    const int o = o0 + ol;
+    const bool live = o < n_out && i0 + il < n_in;          // n_in % 32 == 0: all four columns or none
+    float s = 1.f, zs = 0.f;
+    if (live) {
+      const long trow = (long)((i0 + il) / groupsize) * n_out + o;
+      s = scales[trow];
+      zs = zeros[trow];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = i0 + il + e;
+      uint32_t code = 0;
+      const int i = !live ? -1 : perm ? perm[j] : j;
+      if ((unsigned)i < (unsigned)n_in) {           // (an index outside the row packs code 0, never a stray read)
+        const float w = pk_to_f32<T>(src[(long)o * lds_ + i]);
+        code = (uint32_t)fminf(fmaxf(rintf((w + zs) / s), 0.f), maxq);
+      }
+      cs[ol][il + e] = code;
+    }
+  }
+  __syncthreads();
+  const int ol = tid & 63, g = tid >> 6;
+  const int o = o0 + ol;
+  const int gi = i0 / 32 + g;
+  if (o >= n_out || (gi + 1) * 32 > n_in) return;
+  const uint32_t* v = &cs[ol][32 * g];
+  if (BITS == 3) {
+    uint32_t w[3];
+    pack3_words(v, 1, w);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) qweight[((long)gi * 3 + k) * n_out + o] = (int32_t)w[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      uint32_t w = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) w |= v[8 * k + j] << (4 * j);
+      qweight[((long)gi * 4 + k) * n_out + o] = (int32_t)w;
+    }
+  }
+}
+
 // Packed -> dense:  W[o][i] = scale[g][o] * (code - zero[g][o]),  g = i / groupsize  (tables [G, out], `zero`
 // the INTEGER zero point, so the arithmetic is the solver's own `scale * (q - zero)`, quant.py:10, and every
 // rank of a sharded run reconstructs bit-identical weights).  One thread per (32-input group, output).
-template <typename T, int BITS>
+// PERM: storage column j goes back to input column perm[j] (the act-order format), its grid still that of j / groupsize.
+template <typename T, int BITS, bool PERM = false>
 __global__ __launch_bounds__(256) void dequant_kernel(const int32_t* __restrict__ qweight,
                                                       const float* __restrict__ scale, const float* __restrict__ zero,
-                                                      int n_out, int n_in, int groupsize, T* __restrict__ W, int ldw) {
+                                                      int n_out, int n_in, int groupsize, T* __restrict__ W, int ldw,
+                                                      const int32_t* __restrict__ perm = nullptr) {
   const int o = blockIdx.x * 64 + (threadIdx.x & 63);
   const int gi = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (o >= n_out || (gi + 1) * 32 > n_in) return;
@@ -177,7 +239,8 @@ __global__ __launch_bounds__(256) void dequant_kernel(const int32_t* __restrict_
   for (int k = 0; k < BITS; ++k) w[k] = (uint32_t)qweight[((long)gi * BITS + k) * n_out + o];
   const long trow = (long)((gi * 32) / groupsize) * n_out + o;
   const float s = scale[trow], z = zero[trow];
-  T* dst = W + (long)o * ldw + gi * 32;
+  T* row = W + (long)o * ldw;
+  T* dst = row + gi * 32;
 #pragma unroll
   for (int j = 0; j < 32; ++j) {
     uint32_t v;
@@ -187,9 +250,14 @@ __global__ __launch_bounds__(256) void dequant_kernel(const int32_t* __restrict_
     } else {
       v = (w[j >> 3] >> (4 * (j & 7))) & 15u;
     }
-    const float q = s * ((float)v - z);
-    if constexpr (sizeof(T) == 4) dst[j] = q;
-    else dst[j] = static_cast<T>(q);
+    float q = s * ((float)v - z);
+    // round to fp32 first, like the solver: without this the scatter variant folds the product and the conversion to a
+    // 16-bit type into one v_fma_mixlo (a single rounding), one ulp off the fake-quantized weight at rare ties
+    if constexpr (PERM && sizeof(T) == 2) asm volatile("" : "+v"(q));
+    T* d = PERM ? row + perm[gi * 32 + j] : dst + j;
+    if (PERM && (unsigned)perm[gi * 32 + j] >= (unsigned)n_in) continue;   // never a stray write
+    if constexpr (sizeof(T) == 4) *d = q;
+    else *d = static_cast<T>(q);
   }
 }
 
@@ -254,6 +322,53 @@ extern "C" int gptq_dequant_packed(const int32_t* qweight, const float* scale, c
   else if (w_dtype == GPTQ_F16) { if (bits == 3) DQ(__half, 3); else DQ(__half, 4); }
   else if (w_dtype == GPTQ_BF16) { if (bits == 3) DQ(__hip_bfloat16, 3); else DQ(__hip_bfloat16, 4); }
   else GPTQ_CHECK_ARG(false, "gptq_dequant_packed: unknown dtype %d", w_dtype);
+#undef DQ
+  GPTQ_CHECK_LAUNCH("dequant_kernel");
+  return GPTQ_OK;
+}
+
+extern "C" int gptq_pack_grouped(const void* weight, int w_dtype, int ldw, int out_features, int in_features,
+                                 const float* scales, const float* zeros, int groupsize, const int32_t* perm, int bits,
+                                 int32_t* qweight, gptq_stream_t stream) {
+  GPTQ_CHECK_ARG(weight && scales && zeros && qweight, "gptq_pack_grouped: null pointer");
+  if (int rc = check_pack_shape("gptq_pack_grouped", out_features, in_features, bits)) return rc;
+  GPTQ_CHECK_ARG(ldw >= in_features, "gptq_pack_grouped: leading dimension too small");
+  GPTQ_CHECK_ARG(groupsize > 0 && groupsize % 32 == 0 && in_features % groupsize == 0,
+                 "gptq_pack_grouped: groupsize must be a positive multiple of 32 dividing in_features");
+  const dim3 grid(cdiv(in_features, PT_I), cdiv(out_features, PT_O));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define PG(T, B)                                                                                                    \
+  pack_grouped_kernel<T, B><<<grid, 256, 0, s>>>(static_cast<const T*>(weight), ldw, out_features, in_features, scales, \
+                                                 zeros, groupsize, perm, qweight)
+  if (w_dtype == GPTQ_F32) { if (bits == 3) PG(float, 3); else PG(float, 4); }
+  else if (w_dtype == GPTQ_F16) { if (bits == 3) PG(__half, 3); else PG(__half, 4); }
+  else if (w_dtype == GPTQ_BF16) { if (bits == 3) PG(__hip_bfloat16, 3); else PG(__hip_bfloat16, 4); }
+  else GPTQ_CHECK_ARG(false, "gptq_pack_grouped: unknown dtype %d", w_dtype);
+#undef PG
+  GPTQ_CHECK_LAUNCH("pack_grouped_kernel");
+  return GPTQ_OK;
+}
+
+extern "C" int gptq_dequant_packed_perm(const int32_t* qweight, const float* scale, const float* zero,
+                                        const int32_t* perm, int out_features, int in_features, int bits, int groupsize,
+                                        void* weight, int w_dtype, int ldw, gptq_stream_t stream) {
+  if (!perm)
+    return gptq_dequant_packed(qweight, scale, zero, out_features, in_features, bits, groupsize, weight, w_dtype, ldw,
+                               stream);
+  GPTQ_CHECK_ARG(qweight && scale && zero && weight, "gptq_dequant_packed_perm: null pointer");
+  if (int rc = check_pack_shape("gptq_dequant_packed_perm", out_features, in_features, bits)) return rc;
+  if (groupsize <= 0) groupsize = in_features;
+  GPTQ_CHECK_ARG(groupsize % 32 == 0 && in_features % groupsize == 0 && ldw >= in_features,
+                 "gptq_dequant_packed_perm: groupsize must be a multiple of 32 dividing in_features");
+  const dim3 grid(cdiv(out_features, 64), cdiv(in_features / 32, 4));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define DQ(T, B)                                                                                                    \
+  dequant_kernel<T, B, true><<<grid, 256, 0, s>>>(qweight, scale, zero, out_features, in_features, groupsize,       \
+                                                  static_cast<T*>(weight), ldw, perm)
+  if (w_dtype == GPTQ_F32) { if (bits == 3) DQ(float, 3); else DQ(float, 4); }
+  else if (w_dtype == GPTQ_F16) { if (bits == 3) DQ(__half, 3); else DQ(__half, 4); }
+  else if (w_dtype == GPTQ_BF16) { if (bits == 3) DQ(__hip_bfloat16, 3); else DQ(__hip_bfloat16, 4); }
+  else GPTQ_CHECK_ARG(false, "gptq_dequant_packed_perm: unknown dtype %d", w_dtype);
 #undef DQ
   GPTQ_CHECK_LAUNCH("dequant_kernel");
   return GPTQ_OK;

@@ -20,6 +20,13 @@
 //   * small M is bound by the packed-weight bytes, and N / 256 column tiles cannot fill 256 CUs: the K range is split into
 //     S chunks; each chunk writes its partial sums to the caller's workspace [S][M][N] and a second kernel adds them in
 //     chunk order (fixed order: the same call gives bit-identical Y).
+//
+// Act-order storage (gptq_quant_gemm_perm): packed row k multiplies x[:, perm[k]].  Y is the plain kernel's on the
+// gathered X = x[:, perm], with the same plan, so it is bit-identical to gptq_quant_gemm on a copy of x[:, perm].  The
+// gather happens either inside the X staging (PERM: a thread reads its 8 perm entries once per tile and gathers 8 single
+// elements per row; M <= 4, where it saves the pre-pass launch) or in a pre-pass into the workspace (larger M: the fused
+// form turns one 16-byte load per row and chunk into 8 scattered 2-byte loads, 64 per thread and tile at BM = 128, and
+// was measured 1.3x at M = 16 and 2-4x at M >= 128; the pre-pass costs 1-8 %).
 #include <algorithm>
 
 #include "common.h"
@@ -100,12 +107,12 @@ template <int BITS> __device__ __forceinline__ uint32_t qg_window(const QgWords<
 
 // Grid: (column tiles, row tiles, K chunks).  Block: 256 threads.  `part` != nullptr: write the chunk's partial sums
 // to part[chunk][M][N] (no bias); otherwise write Y (+ bias).
-template <int BITS, typename XT, typename YT, bool GROUPED, int MSUB, int WM>
+template <int BITS, typename XT, typename YT, bool GROUPED, int MSUB, int WM, bool PERM = false>
 __global__ __launch_bounds__(256) void qgemm_kernel(const XT* __restrict__ x, int ldx, int M, const int32_t* __restrict__ qw,
                                                     const float* __restrict__ scales, const float* __restrict__ zeros,
                                                     const float* __restrict__ bias, int K, int N, int groupsize,
                                                     int chunk_steps, YT* __restrict__ y, int ldy, float* __restrict__ part,
-                                                    bool xvec, bool wvec) {
+                                                    bool xvec, bool wvec, const int32_t* __restrict__ perm = nullptr) {
   typedef typename QgFrag<XT>::type F;
   constexpr int WN = 4 / WM;
   constexpr int BM = WM * MSUB * 16, BN = WN * 64;
@@ -130,13 +137,27 @@ __global__ __launch_bounds__(256) void qgemm_kernel(const XT* __restrict__ x, in
   auto load_x = [&](int tile) {
     const int k = (kbeg + 4 * tile) * 32 + 8 * (tid & 15);
     const bool kin = k < kend * 32;
+    int pk[8];                                               // PERM: the input columns of the chunk's 8 storage rows
+    if (PERM && kin) {
+      const int4 a = *reinterpret_cast<const int4*>(perm + k), b = *reinterpret_cast<const int4*>(perm + k + 4);
+      pk[0] = a.x; pk[1] = a.y; pk[2] = a.z; pk[3] = a.w; pk[4] = b.x; pk[5] = b.y; pk[6] = b.z; pk[7] = b.w;
+    }
 #pragma unroll
     for (int i = 0; i < XCH; ++i) {
       const int row = m0 + (tid >> 4) + 16 * i;
       xr[i] = make_uint4(0, 0, 0, 0);
       if (kin && row < M) {
         const XT* p = x + (size_t)row * ldx + k;
-        if (xvec) {
+        if (PERM) {
+          const uint16_t* q = reinterpret_cast<const uint16_t*>(x + (size_t)row * ldx);
+          uint32_t e[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) e[j] = (unsigned)pk[j] < (unsigned)K ? q[pk[j]] : 0u;   // never a stray read
+          xr[i].x = e[0] | (e[1] << 16);
+          xr[i].y = e[2] | (e[3] << 16);
+          xr[i].z = e[4] | (e[5] << 16);
+          xr[i].w = e[6] | (e[7] << 16);
+        } else if (xvec) {
           xr[i] = *reinterpret_cast<const uint4*>(p);
         } else {
           const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
@@ -274,6 +295,25 @@ __global__ __launch_bounds__(256) void qgemm_kernel(const XT* __restrict__ x, in
     }
 }
 
+// Gather pre-pass of the act-order GEMM: xg[m][j] = x[m][perm[j]] (16-bit elements), xg row-major with K columns.
+// Thread = 8 consecutive j of one row: two 16-byte loads of perm, 8 gathered elements (the row sits in L2), one 16-byte
+// store.  An index outside the row gathers 0.
+__global__ __launch_bounds__(256) void qgemm_gather_kernel(const uint16_t* __restrict__ x, int ldx, int M, int K,
+                                                           const int32_t* __restrict__ perm, uint16_t* __restrict__ xg) {
+  const int j = (blockIdx.x * 256 + threadIdx.x) * 8;
+  if (j >= K) return;
+  const int4 a = *reinterpret_cast<const int4*>(perm + j), b = *reinterpret_cast<const int4*>(perm + j + 4);
+  const int pk[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  for (int row = blockIdx.y; row < M; row += gridDim.y) {
+    const uint16_t* q = x + (size_t)row * ldx;
+    uint32_t e[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) e[t] = (unsigned)pk[t] < (unsigned)K ? q[pk[t]] : 0u;
+    *reinterpret_cast<uint4*>(xg + (size_t)row * K + j) =
+        make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
+  }
+}
+
 // Y = sum over the S chunk partials in chunk order (+ bias), rounded once
 template <typename YT>
 __global__ __launch_bounds__(256) void qgemm_reduce_kernel(const float* __restrict__ part, int S, int M, int N,
@@ -314,41 +354,64 @@ static size_t qg_workspace_bytes(const QgPlan& p, int M, int N) {
   return p.S > 1 ? (size_t)p.S * M * N * sizeof(float) : 0;
 }
 
+// Act-order GEMM: up to this M the gather is fused into the X staging, above it a pre-pass gathers X into the workspace
+// ("act-order GEMM": measured on the Llama-7B Linears).
+static int qg_perm_fused_max_m() {
+  static const int m = tune_knob("GPTQ_QG_PERM_FUSED_M", 4);
+  return m;
+}
+static bool qg_perm_prepass(int M) { return M > qg_perm_fused_max_m(); }
+// bytes of the partials (rounded up to 256) + the gathered X of the pre-pass
+static size_t qg_perm_workspace_bytes(const QgPlan& p, int M, int K, int N) {
+  const size_t part = qg_workspace_bytes(p, M, N);
+  return qg_perm_prepass(M) ? align_up(part, 256) + (size_t)M * K * sizeof(uint16_t) : part;
+}
+
 template <int BITS, typename XT, typename YT, bool GROUPED>
 static void qg_launch_cfg(const QgPlan& p, const void* x, int ldx, int M, const int32_t* qw, const float* sc,
                           const float* zr, const float* bias, int K, int N, int groupsize, void* y, int ldy, float* part,
-                          bool xvec, bool wvec, hipStream_t s) {
+                          bool xvec, bool wvec, hipStream_t s, const int32_t* perm) {
   const dim3 grid(cdiv(N, p.bn), cdiv(M, p.bm), p.S);
   const XT* xp = static_cast<const XT*>(x);
   YT* yp = static_cast<YT*>(y);
-#define QG_GO(MS, WMV)                                                                                             \
-  qgemm_kernel<BITS, XT, YT, GROUPED, MS, WMV><<<grid, 256, 0, s>>>(xp, ldx, M, qw, sc, zr, bias, K, N, groupsize, \
-                                                                   p.chunk_steps, yp, ldy, part, xvec, wvec)
-  if (p.wm == 2) QG_GO(4, 2);
-  else if (p.msub == 4) QG_GO(4, 1);
-  else if (p.msub == 2) QG_GO(2, 1);
-  else QG_GO(1, 1);
+#define QG_GO(MS, WMV, PM)                                                                                          \
+  qgemm_kernel<BITS, XT, YT, GROUPED, MS, WMV, PM><<<grid, 256, 0, s>>>(xp, ldx, M, qw, sc, zr, bias, K, N,         \
+                                                                       groupsize, p.chunk_steps, yp, ldy, part, xvec, \
+                                                                       wvec, perm)
+  if constexpr (GROUPED) {                                 // the act-order format always has grouped grids
+    if (perm) {
+      if (p.wm == 2) QG_GO(4, 2, true);
+      else if (p.msub == 4) QG_GO(4, 1, true);
+      else if (p.msub == 2) QG_GO(2, 1, true);
+      else QG_GO(1, 1, true);
+      return;
+    }
+  }
+  if (p.wm == 2) QG_GO(4, 2, false);
+  else if (p.msub == 4) QG_GO(4, 1, false);
+  else if (p.msub == 2) QG_GO(2, 1, false);
+  else QG_GO(1, 1, false);
 #undef QG_GO
 }
 
 template <int BITS, typename XT, typename YT>
 static void qg_launch(const QgPlan& p, const void* x, int ldx, int M, const int32_t* qw, const float* sc,
                       const float* zr, const float* bias, int K, int N, int groupsize, void* y, int ldy, float* part,
-                      bool xvec, bool wvec, hipStream_t s) {
+                      bool xvec, bool wvec, hipStream_t s, const int32_t* perm) {
   if (groupsize > 0)
-    qg_launch_cfg<BITS, XT, YT, true>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s);
+    qg_launch_cfg<BITS, XT, YT, true>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s, perm);
   else
-    qg_launch_cfg<BITS, XT, YT, false>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s);
+    qg_launch_cfg<BITS, XT, YT, false>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s, perm);
 }
 
 template <int BITS, typename XT>
 static void qg_launch_y(int y_dtype, const QgPlan& p, const void* x, int ldx, int M, const int32_t* qw, const float* sc,
                         const float* zr, const float* bias, int K, int N, int groupsize, void* y, int ldy, float* part,
-                        bool xvec, bool wvec, hipStream_t s) {
+                        bool xvec, bool wvec, hipStream_t s, const int32_t* perm) {
   if (part) y_dtype = GPTQ_F32;                          // the partials are fp32; Y is written by the reduction
-  if (y_dtype == GPTQ_F32) qg_launch<BITS, XT, float>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s);
-  else if (y_dtype == GPTQ_F16) qg_launch<BITS, XT, __half>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s);
-  else qg_launch<BITS, XT, __hip_bfloat16>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s);
+  if (y_dtype == GPTQ_F32) qg_launch<BITS, XT, float>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s, perm);
+  else if (y_dtype == GPTQ_F16) qg_launch<BITS, XT, __half>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s, perm);
+  else qg_launch<BITS, XT, __hip_bfloat16>(p, x, ldx, M, qw, sc, zr, bias, K, N, groupsize, y, ldy, part, xvec, wvec, s, perm);
 }
 
 }  // namespace gptq
@@ -361,10 +424,10 @@ extern "C" size_t gptq_quant_gemm_workspace_bytes(int M, int K, int N, int bits,
   return qg_workspace_bytes(qg_plan(M, K, N, bits), M, N);
 }
 
-extern "C" int gptq_quant_gemm(const void* x, int x_dtype, int ldx, int M, const int32_t* qweight, const float* scales,
-                               const float* zeros, const float* bias, int K, int N, int bits, int groupsize, void* y,
-                               int y_dtype, int ldy, void* workspace, size_t workspace_bytes, gptq_stream_t stream) {
-  const char* who = "gptq_quant_gemm";
+static int quant_gemm_impl(const char* who, const void* x, int x_dtype, int ldx, int M, const int32_t* qweight,
+                           const float* scales, const float* zeros, const int32_t* perm, const float* bias, int K, int N,
+                           int bits, int groupsize, void* y, int y_dtype, int ldy, void* workspace,
+                           size_t workspace_bytes, hipStream_t s) {
   GPTQ_CHECK_ARG(x && qweight && scales && zeros && y, "%s: null pointer", who);
   GPTQ_CHECK_ARG(bits == 3 || bits == 4, "%s: bits must be 3 or 4", who);
   GPTQ_CHECK_ARG(M >= 1 && N >= 1 && K >= 32 && K % 32 == 0, "%s: need M >= 1, N >= 1 and K a positive multiple of 32", who);
@@ -373,23 +436,34 @@ extern "C" int gptq_quant_gemm(const void* x, int x_dtype, int ldx, int M, const
   GPTQ_CHECK_ARG(ldx >= K && ldy >= N, "%s: ldx must be >= K and ldy >= N", who);
   GPTQ_CHECK_ARG(groupsize <= 0 || (groupsize % 32 == 0 && K % groupsize == 0),
                  "%s: groupsize must be a multiple of 32 that divides K", who);
+  GPTQ_CHECK_ARG(!perm || groupsize > 0, "%s: perm needs grouped grids (groupsize > 0)", who);
+  GPTQ_CHECK_ARG(!perm || reinterpret_cast<uintptr_t>(perm) % 16 == 0, "%s: perm must be 16-byte aligned", who);
   GPTQ_CHECK_ARG((size_t)M * N * 16 < ((size_t)1 << 62) && (size_t)M * ldx < ((size_t)1 << 62), "%s: shape too large", who);
   const QgPlan p = qg_plan(M, K, N, bits);
   GPTQ_CHECK_ARG(cdiv(M, p.bm) <= 65535, "%s: M too large", who);
-  const size_t need = qg_workspace_bytes(p, M, N);
+  const size_t need = perm ? qg_perm_workspace_bytes(p, M, K, N) : qg_workspace_bytes(p, M, N);
   GPTQ_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace),
-                 "%s: workspace of %zu bytes needed (gptq_quant_gemm_workspace_bytes)", who, need);
-  float* part = need ? static_cast<float*>(workspace) : nullptr;
+                 "%s: workspace of %zu bytes needed (%s_workspace_bytes)", who, need, who);
+  float* part = qg_workspace_bytes(p, M, N) ? static_cast<float*>(workspace) : nullptr;
+  if (perm && qg_perm_prepass(M)) {                      // gather X into the workspace, then the plain kernel
+    GPTQ_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: workspace must be 16-byte aligned", who);
+    uint16_t* xg = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + align_up(qg_workspace_bytes(p, M, N), 256));
+    const dim3 gg(cdiv(K, 256 * 8), std::min(M, 65535));
+    qgemm_gather_kernel<<<gg, 256, 0, s>>>(static_cast<const uint16_t*>(x), ldx, M, K, perm, xg);
+    GPTQ_CHECK_LAUNCH(who);
+    x = xg;
+    ldx = K;
+    perm = nullptr;
+  }
   const bool xvec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
   const bool wvec = reinterpret_cast<uintptr_t>(qweight) % 16 == 0 && N % 4 == 0;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const int gs = groupsize > 0 ? groupsize : 0;
   if (x_dtype == GPTQ_F16) {
-    if (bits == 3) qg_launch_y<3, __half>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s);
-    else qg_launch_y<4, __half>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s);
+    if (bits == 3) qg_launch_y<3, __half>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm);
+    else qg_launch_y<4, __half>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm);
   } else {
-    if (bits == 3) qg_launch_y<3, __hip_bfloat16>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s);
-    else qg_launch_y<4, __hip_bfloat16>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s);
+    if (bits == 3) qg_launch_y<3, __hip_bfloat16>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm);
+    else qg_launch_y<4, __hip_bfloat16>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm);
   }
   GPTQ_CHECK_LAUNCH(who);
   if (part) {
@@ -401,4 +475,25 @@ extern "C" int gptq_quant_gemm(const void* x, int x_dtype, int ldx, int M, const
     GPTQ_CHECK_LAUNCH(who);
   }
   return GPTQ_OK;
+}
+
+extern "C" int gptq_quant_gemm(const void* x, int x_dtype, int ldx, int M, const int32_t* qweight, const float* scales,
+                               const float* zeros, const float* bias, int K, int N, int bits, int groupsize, void* y,
+                               int y_dtype, int ldy, void* workspace, size_t workspace_bytes, gptq_stream_t stream) {
+  return quant_gemm_impl("gptq_quant_gemm", x, x_dtype, ldx, M, qweight, scales, zeros, nullptr, bias, K, N, bits,
+                         groupsize, y, y_dtype, ldy, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t gptq_quant_gemm_perm_workspace_bytes(int M, int K, int N, int bits, int groupsize) {
+  (void)groupsize;
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32 || (bits != 3 && bits != 4)) return 0;
+  return qg_perm_workspace_bytes(qg_plan(M, K, N, bits), M, K, N);
+}
+
+extern "C" int gptq_quant_gemm_perm(const void* x, int x_dtype, int ldx, int M, const int32_t* qweight,
+                                    const float* scales, const float* zeros, const int32_t* perm, const float* bias, int K,
+                                    int N, int bits, int groupsize, void* y, int y_dtype, int ldy, void* workspace,
+                                    size_t workspace_bytes, gptq_stream_t stream) {
+  return quant_gemm_impl("gptq_quant_gemm_perm", x, x_dtype, ldx, M, qweight, scales, zeros, perm, bias, K, N, bits,
+                         groupsize, y, y_dtype, ldy, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }

@@ -126,27 +126,74 @@ def pack_codes(codes, bits):
     return qweight
 
 
-def dequant_packed(qweight, scale, zero, bits, groupsize, dtype=torch.float16):
+def check_perm(perm, n_in, ref, who):
+    """The act-order permutation as the kernels take it: int32 [n_in] on `ref`'s device, contiguous and 16-byte aligned.
+    Raises ValueError before any launch."""
+    if perm.dtype != torch.int32:
+        raise ValueError(f"{who}: perm must be int32, got {perm.dtype}")
+    if perm.dim() != 1 or perm.numel() != n_in:
+        raise ValueError(f"{who}: perm must hold {n_in} entries (one per input feature), got shape {tuple(perm.shape)}")
+    if perm.device != ref.device:
+        raise ValueError(f"{who}: perm is on {perm.device}, the operands on {ref.device}")
+    p = perm.contiguous()
+    return p if p.data_ptr() % 16 == 0 else p.clone()
+
+
+def dequant_packed(qweight, scale, zero, bits, groupsize, dtype=torch.float16, perm=None):
     """int32 [in/32*bits, out] + grids [G, out] (`zero` = integer zero point) -> dense [out, in] weights,
-    computed as scale * (code - zero) like the solver itself (quant.py:10)."""
-    dev = _dev_of(qweight)
+    computed as scale * (code - zero) like the solver itself (quant.py:10).  `perm` (int32 [in]): the act-order format,
+    storage row j is written back to input column perm[j]."""
     n_out = qweight.shape[1]
     n_in = qweight.shape[0] // bits * 32
+    if perm is not None:
+        perm = check_perm(perm, n_in, qweight, "dequant_packed")
+    dev = _dev_of(qweight)
     W = torch.empty((n_out, n_in), dtype=dtype, device=dev)
     s = scale.to(torch.float32).contiguous()
     z = zero.to(torch.float32).contiguous()
     with torch.cuda.device(dev):
-        _lib.call("gptq_dequant_packed", _lib.ptr(qweight.contiguous()), _lib.ptr(s), _lib.ptr(z), n_out, n_in, int(bits),
-                  int(groupsize), _lib.ptr(W), _lib.dtype_code(W), W.stride(0), _lib.stream(dev))
+        if perm is None:
+            _lib.call("gptq_dequant_packed", _lib.ptr(qweight.contiguous()), _lib.ptr(s), _lib.ptr(z), n_out, n_in,
+                      int(bits), int(groupsize), _lib.ptr(W), _lib.dtype_code(W), W.stride(0), _lib.stream(dev))
+        else:
+            _lib.call("gptq_dequant_packed_perm", _lib.ptr(qweight.contiguous()), _lib.ptr(s), _lib.ptr(z), _lib.ptr(perm),
+                      n_out, n_in, int(bits), int(groupsize), _lib.ptr(W), _lib.dtype_code(W), W.stride(0),
+                      _lib.stream(dev))
     return W
 
 
-def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_dtype=None):
+def pack_grouped(weight, scales, zeros, groupsize, bits, perm=None):
+    """[out, in] weights on grouped grids -> int32 [in/32*bits, out] (gptq_pack_grouped).  scales / zeros: [in/groupsize,
+    out] (zeros = zero*scale).  With `perm` (int32 [in]) storage row j holds input column perm[j] on the grid of group
+    j // groupsize: the act-order format.  Each code is clamp(round((w + zeros) / scales), 0, 2^bits - 1)."""
+    bits, groupsize = int(bits), int(groupsize)
+    w = weight if weight.stride(-1) == 1 else weight.contiguous()
+    n_out, n_in = w.shape
+    if groupsize <= 0 or groupsize % 32 or n_in % groupsize:
+        raise ValueError("pack_grouped: groupsize must be a positive multiple of 32 that divides in_features")
+    want = (n_in // groupsize, n_out)
+    if tuple(scales.shape) != want or tuple(zeros.shape) != want:
+        raise ValueError(f"pack_grouped: scales / zeros must be {want}")
+    if perm is not None:
+        perm = check_perm(perm, n_in, w, "pack_grouped")
+    dev = _dev_of(w)
+    s = scales.to(device=dev, dtype=torch.float32).contiguous()
+    z = zeros.to(device=dev, dtype=torch.float32).contiguous()
+    qweight = torch.empty((n_in // 32 * bits, n_out), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("gptq_pack_grouped", _lib.ptr(w), _lib.dtype_code(w), w.stride(0), n_out, n_in, _lib.ptr(s),
+                  _lib.ptr(z), groupsize, _lib.ptr(perm), bits, _lib.ptr(qweight), _lib.stream(dev))
+    return qweight
+
+
+def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_dtype=None, perm=None):
     """x [..., K] (fp16 / bf16) times the packed weights -> [..., N] in `out_dtype` (default x.dtype), through the
     dequant GEMM of libgptq_hip.so (gptq_quant_gemm): the multi-token forward of the packed Linears.
 
     qweight int32 [K/32*bits, N] (the modules' layouts); scales / zeros (zeros = zero*scale) hold N values for per-row
-    grids (groupsize <= 0) or [K/groupsize, N] for grouped ones; bias [N] or None.  fp32 accumulation, one rounding."""
+    grids (groupsize <= 0) or [K/groupsize, N] for grouped ones; bias [N] or None.  fp32 accumulation, one rounding.
+    `perm` (int32 [K], grouped grids only): the act-order format, packed row k multiplies x[..., perm[k]]
+    (gptq_quant_gemm_perm); the result is bit-identical to quant_matmul(x[..., perm], ...) without it."""
     if x.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"quant_matmul: x must be fp16 or bf16, got {x.dtype}")
     if out_dtype is None:
@@ -172,6 +219,10 @@ def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_d
         raise ValueError(f"quant_matmul: per-row scales / zeros must hold {N} values")
     if bias is not None and bias.numel() != N:
         raise ValueError(f"quant_matmul: bias must hold {N} values")
+    if perm is not None:
+        if groupsize <= 0:
+            raise ValueError("quant_matmul: perm (the act-order format) needs grouped grids")
+        perm = check_perm(perm, K, x, "quant_matmul")
     for name, t in (("x", x), ("qweight", qweight), ("scales", scales), ("zeros", zeros)):
         _lib.require_gpu(t, name)
     if bias is not None:
@@ -190,12 +241,20 @@ def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_d
     z = zeros.to(torch.float32).contiguous()
     b = bias.to(torch.float32).contiguous() if bias is not None else None
     lib = _lib.load()
-    nbytes = lib.gptq_quant_gemm_workspace_bytes(M, K, N, bits, groupsize)
+    if perm is None:
+        nbytes = lib.gptq_quant_gemm_workspace_bytes(M, K, N, bits, groupsize)
+    else:
+        nbytes = lib.gptq_quant_gemm_perm_workspace_bytes(M, K, N, bits, groupsize)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
     with torch.cuda.device(dev):
-        _lib.call("gptq_quant_gemm", _lib.ptr(x2), _lib.dtype_code(x2), x2.stride(0), M, _lib.ptr(qw), _lib.ptr(s),
-                  _lib.ptr(z), _lib.ptr(b), K, N, bits, groupsize, _lib.ptr(y), _lib.dtype_code(y), y.stride(0),
-                  _lib.ptr(ws), nbytes, _lib.stream(dev))
+        if perm is None:
+            _lib.call("gptq_quant_gemm", _lib.ptr(x2), _lib.dtype_code(x2), x2.stride(0), M, _lib.ptr(qw), _lib.ptr(s),
+                      _lib.ptr(z), _lib.ptr(b), K, N, bits, groupsize, _lib.ptr(y), _lib.dtype_code(y), y.stride(0),
+                      _lib.ptr(ws), nbytes, _lib.stream(dev))
+        else:
+            _lib.call("gptq_quant_gemm_perm", _lib.ptr(x2), _lib.dtype_code(x2), x2.stride(0), M, _lib.ptr(qw),
+                      _lib.ptr(s), _lib.ptr(z), _lib.ptr(perm), _lib.ptr(b), K, N, bits, groupsize, _lib.ptr(y),
+                      _lib.dtype_code(y), y.stride(0), _lib.ptr(ws), nbytes, _lib.stream(dev))
     return y.reshape(outshape)
 
 
@@ -293,40 +352,88 @@ class QuantGroupLinear(nn.Module):
 
     The reference cannot pack grouped models (Quant3Linear keeps per-row scalars, quant.py:144-145, and
     fasterquant leaves only the LAST group's grid in the quantizer).  Buffers: `qweight` int32
-    [in/32*bits, out] (same bit layouts as the per-row modules, original column order), `scales` /
-    `zeros` fp32 [in/groupsize, out] (`zeros` = zero*scale), `bias`.  Filled from a finished `GPTQ`
-    object (`codes`, `group_scale`, `group_zero`); valid for static groups or runs without act-order.
+    [in/32*bits, out] (same bit layouts as the per-row modules), `scales` / `zeros` fp32 [in/groupsize, out]
+    (`zeros` = zero*scale), `bias`.  Runs without act-order and runs with static groups store the codes in original
+    column order.  `act_order=True` is the format of act-order runs with dynamic groups, whose groups are consecutive
+    positions of the permuted column order: storage row j holds input column perm[j] on the grid of group j // groupsize,
+    and an int32 buffer `perm` [in] is added ("Grouped and act-order checkpoints").
     """
 
-    def __init__(self, bits, groupsize, infeatures, outfeatures, multi_token=False):
+    def __init__(self, bits, groupsize, infeatures, outfeatures, multi_token=False, act_order=False):
         super().__init__()
         self.multi_token = multi_token
         if bits not in (3, 4) or groupsize % 32 or infeatures % groupsize:
             raise ValueError("QuantGroupLinear: bits in {3,4}, groupsize % 32 == 0, in_features % groupsize == 0")
         self.bits, self.groupsize = bits, groupsize
+        self.act_order = bool(act_order)
         self.register_buffer('qweight', torch.zeros((infeatures // 32 * bits, outfeatures), dtype=torch.int))
         self.register_buffer('scales', torch.zeros((infeatures // groupsize, outfeatures)))
         self.register_buffer('zeros', torch.zeros((infeatures // groupsize, outfeatures)))
         self.register_buffer('bias', torch.zeros(outfeatures))
+        if self.act_order:
+            self.register_buffer('perm', torch.arange(infeatures, dtype=torch.int32))
 
     @classmethod
     def from_gptq(cls, solver, bits, multi_token=False):
-        """Build from a `GPTQ` object after `fasterquant(groupsize=g, ...)`."""
+        """Build from a `GPTQ` object after `fasterquant(groupsize=g, ...)`.  Act-order with dynamic groups gives an
+        `act_order=True` module (codes packed in the permuted order); every other grouped run today's format."""
         gs, gz = solver.group_scale, solver.group_zero          # [out, G]
         if gs is None:
             raise ValueError("QuantGroupLinear.from_gptq: the solver ran without groups")
-        if solver.perm is not None and not getattr(solver, "static_groups", False):
-            raise ValueError("QuantGroupLinear.from_gptq: act-order needs static groups for a g_idx-free format")
+        act = solver.perm is not None and not getattr(solver, "static_groups", False)
         n_out, n_in = solver.codes.shape
-        m = cls(bits, n_in // gs.shape[1], n_in, n_out, multi_token=multi_token)
-        m.qweight = pack_codes(solver.codes, bits)
+        m = cls(bits, n_in // gs.shape[1], n_in, n_out, multi_token=multi_token, act_order=act)
+        if act:
+            perm = solver.perm.to(torch.int32)
+            m.qweight = pack_codes(solver.codes.index_select(1, perm.long()), bits)
+            m.perm = perm.contiguous().clone()
+        else:
+            m.qweight = pack_codes(solver.codes, bits)
         m.scales = gs.t().contiguous()
         m.zeros = (gz * gs).t().contiguous()
         bias = getattr(solver.layer, "bias", None)
         m.bias = bias.detach().clone().float() if bias is not None else torch.zeros(n_out, device=gs.device)
         return m
 
+    def pack(self, linear, group_scale, group_zero, perm=None):
+        """Fill the buffers from a Linear holding fake-quantized weights and its grids `group_scale` / `group_zero`
+        [out, G] (`group_zero` = the integer zero point), as the driver's quantizers carry them.  `perm` (act-order
+        modules only): the solver's permutation.  Like the per-row modules' `pack`, the packing runs on the GPU and the
+        buffers go back to the Linear's device."""
+        if (perm is not None) != self.act_order:
+            raise ValueError("QuantGroupLinear.pack: perm is needed exactly for act_order=True modules")
+        home = linear.weight.device
+        dev = home if home.type == 'cuda' else torch.device('cuda', torch.cuda.current_device()) \
+            if torch.cuda.is_available() else None
+        if dev is None:
+            raise _lib.GptqHipError("packing needs an MI355X device; gptq_amd has no CPU path")
+        gs = group_scale.to(device=dev, dtype=torch.float32)
+        scales = gs.t().contiguous()
+        zeros = (group_zero.to(device=dev, dtype=torch.float32) * gs).t().contiguous()
+        p = perm.to(device=dev, dtype=torch.int32) if perm is not None else None
+        qweight = pack_grouped(linear.weight.data.to(dev), scales, zeros, self.groupsize, self.bits, p)
+        self.qweight = qweight.to(home)
+        self.scales = scales.to(home)
+        self.zeros = zeros.to(home)
+        if linear.bias is not None:
+            self.bias = linear.bias.detach().float().clone().to(home)
+        if p is not None:
+            self.perm = p.clone().to(home)
+
+    @property
+    def g_idx(self):
+        """Group index of every ORIGINAL input column (int32 [in]), what other GPTQ tools call g_idx:
+        g_idx[perm[j]] = j // groupsize for act-order modules, k // groupsize otherwise.  Derived, not stored."""
+        n_in = self.qweight.shape[0] // self.bits * 32
+        grp = torch.arange(n_in, dtype=torch.int32, device=self.qweight.device) // self.groupsize
+        if not self.act_order:
+            return grp
+        g = torch.empty_like(grp)
+        g[self.perm.long()] = grp
+        return g
+
     def forward(self, x):
+        perm = self.perm if self.act_order else None
         if x.shape[-1] == x.numel():
             outshape = list(x.shape)
             y = self.bias.clone().float()
@@ -334,10 +441,11 @@ class QuantGroupLinear(nn.Module):
             dtype = x.dtype
             xv = x if x.dtype in (torch.float16, torch.float32) else x.float()
             quant_cuda.vecquant_matmul_grouped(xv.reshape(-1), self.qweight, y, self.scales, self.zeros,
-                                               self.bits, self.groupsize)
+                                               self.bits, self.groupsize, perm=perm)
             return y.to(dtype).reshape(outshape)
         if self.multi_token:
-            return quant_matmul(x, self.qweight, self.scales, self.zeros, self.bits, self.groupsize, self.bias)
+            return quant_matmul(x, self.qweight, self.scales, self.zeros, self.bits, self.groupsize, self.bias,
+                                perm=perm)
         raise ValueError('Only supports a single token currently.')
 
 

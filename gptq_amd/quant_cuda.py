@@ -67,8 +67,12 @@ def vecquant4matmul(vec, mat, mul, scales, zeros):
     _run("gptq_vecquant4matmul", 4, vec, mat, mul, scales, zeros, vec.dtype if vec.dtype == torch.float16 else torch.float32)
 
 
-def vecquant_matmul_grouped(vec, mat, mul, scales, zeros, bits, groupsize):
-    """Grouped-grid mat-vec: scales / zeros are [in/groupsize, out], zeros = zero*scale."""
+def vecquant_matmul_grouped(vec, mat, mul, scales, zeros, bits, groupsize, perm=None):
+    """Grouped-grid mat-vec: scales / zeros are [in/groupsize, out], zeros = zero*scale.  `perm` (int32
+    [in]): the act-order format, packed row k multiplies vec[perm[k]] (gptq_vecquant_matmul_grouped_perm)."""
+    if perm is not None:
+        from .quant import check_perm
+        perm = check_perm(perm, mat.shape[0] // bits * 32, vec, "vecquant_matmul_grouped")
     for name, t in (("vec", vec), ("mat", mat), ("mul", mul), ("scales", scales), ("zeros", zeros)):
         _lib.require_gpu(t, name)
     if vec.dtype not in (torch.float32, torch.float16):
@@ -88,5 +92,10 @@ def vecquant_matmul_grouped(vec, mat, mul, scales, zeros, bits, groupsize):
     z = zeros.to(torch.float32).contiguous()
     dev = vec.device
     with torch.cuda.device(dev):
-        _lib.call("gptq_vecquant_matmul_grouped", _lib.ptr(v), _lib.dtype_code(v), _lib.ptr(mat), _lib.ptr(mul),
-                  _lib.ptr(s), _lib.ptr(z), height, width, int(bits), int(groupsize), _lib.stream(dev))
+        if perm is None:
+            _lib.call("gptq_vecquant_matmul_grouped", _lib.ptr(v), _lib.dtype_code(v), _lib.ptr(mat), _lib.ptr(mul),
+                      _lib.ptr(s), _lib.ptr(z), height, width, int(bits), int(groupsize), _lib.stream(dev))
+        else:
+            _lib.call("gptq_vecquant_matmul_grouped_perm", _lib.ptr(v), _lib.dtype_code(v), _lib.ptr(mat),
+                      _lib.ptr(mul), _lib.ptr(s), _lib.ptr(z), _lib.ptr(perm), height, width, int(bits), int(groupsize),
+                      _lib.stream(dev))

@@ -359,6 +359,8 @@ def _quantize_sequential(model, dataloader, dev, args, group, world, rank, timin
             for n in names:
                 key = f"{fam['prefix']}.{i}.{n}"
                 quantizers[key] = solvers[n].quantizer
+                if args.groupsize > 0:
+                    _attach_groups(solvers[n], args.groupsize, static_groups)
                 records.append(dict(name=key, error=solvers[n].error))
                 solvers[n].free()
             if args.cache_outputs and len(groups) > 1:          # (a single group: its Linears run once after the solve anyway)
@@ -391,6 +393,18 @@ def _quantize_sequential(model, dataloader, dev, args, group, world, rank, timin
         timings["blocks"] = len(layers)
         timings["wall_s"] = time.perf_counter() - t_wall
     return quantizers
+
+
+def _attach_groups(solver, groupsize, static_groups):
+    """A grouped solve leaves the grid of its LAST group in `quantizer.scale / zero` (the reference's limit); what packing
+    needs goes onto the quantizer before the solver is freed: `group_scale` / `group_zero` [R, G] (integer zero point),
+    `perm` (int32 act-order permutation or None), `groupsize` and `static_groups`."""
+    q = solver.quantizer
+    q.group_scale = solver.group_scale
+    q.group_zero = solver.group_zero
+    q.perm = solver.perm.to(torch.int32) if solver.perm is not None else None
+    q.groupsize = int(groupsize)
+    q.static_groups = bool(static_groups)
 
 
 @torch.no_grad()
@@ -477,24 +491,42 @@ def _set_module(root, dotted, new):
 def pack_model(model, quantizers, bits, faster=False, multi_token=False):
     """Replace every quantized Linear by a packed module in place, like `opt_pack3` (opt.py:362-373).
 
-    Per-row grids only (what `Quant3Linear` / `Quant4Linear` can hold): run the quantization with
-    groupsize = -1.  The packing itself happens on the GPU (the reference loops over rows in numpy,
-    "TODO: perform packing on GPU", opt.py:361).  `multi_token=True` lets the packed model run inputs of several
-    tokens (prefill, `eval_ppl`) through the dequant GEMM."""
-    from .quant import Quant3Linear, Quant4Linear
+    Per-row runs (groupsize = -1) give `Quant3Linear` / `Quant4Linear`.  Grouped runs, whose quantizers carry the group
+    grids (`group_scale`, see quantize_sequential), give `QuantGroupLinear`; act-order with dynamic groups packs in the
+    permuted order with a `perm` buffer (`act_order=True`), every other grouped run in original order.  The packing
+    itself happens on the GPU (the reference loops over rows in numpy, "TODO: perform packing on GPU", opt.py:361).
+    `multi_token=True` lets the packed model run inputs of several tokens (prefill, `eval_ppl`) through the dequant
+    GEMM.  (`faster` applies to the 3-bit per-row module only.)"""
+    from .quant import Quant3Linear, Quant4Linear, QuantGroupLinear
     cls = {3: Quant3Linear, 4: Quant4Linear}[bits]
     layers = find_layers(model)
     for name, q in quantizers.items():
         lin = layers[name]
-        packed = cls(lin.in_features, lin.out_features, faster=faster, multi_token=multi_token)
-        packed.pack(lin, q.scale.float(), q.zero.float())
+        if getattr(q, "group_scale", None) is not None:
+            act = q.perm is not None and not q.static_groups
+            packed = QuantGroupLinear(bits, q.groupsize, lin.in_features, lin.out_features, multi_token=multi_token,
+                                      act_order=act)
+            packed.pack(lin, q.group_scale, q.group_zero, perm=q.perm if act else None)
+        else:
+            packed = cls(lin.in_features, lin.out_features, faster=faster, multi_token=multi_token)
+            packed.pack(lin, q.scale.float(), q.zero.float())
         _set_module(model, name, packed)
     return model
 
 
-def make_packed_skeleton(model, names, bits, faster=False, multi_token=False):
+def make_packed_skeleton(model, names, bits, faster=False, multi_token=False, groupsize=-1, act_order=False):
     """Empty packed modules for `names` (the load side of opt.py:375-402): load_state_dict then fills
-    `qweight / scales / zeros / bias`."""
+    `qweight / scales / zeros / bias` (and `perm`).  groupsize > 0 builds `QuantGroupLinear` modules for checkpoints of
+    grouped runs; `act_order=True` gives them the `perm` buffer of the act-order format (act-order runs with dynamic
+    groups -- act-order runs with static groups use the plain grouped format and load with act_order=False)."""
+    if groupsize > 0:
+        from .quant import QuantGroupLinear
+        layers = find_layers(model)
+        for name in names:
+            lin = layers[name]
+            _set_module(model, name, QuantGroupLinear(bits, groupsize, lin.in_features, lin.out_features,
+                                                      multi_token=multi_token, act_order=act_order))
+        return model
     from .quant import make_quant3, make_quant4
     (make_quant3 if bits == 3 else make_quant4)(model, names, faster=faster, multi_token=multi_token)
     return model

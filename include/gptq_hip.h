@@ -233,12 +233,29 @@ int gptq_pack_weights(const void* weight, int w_dtype, int ldw, int out_features
 int gptq_pack_codes(const uint8_t* codes, int ldc, int out_features, int in_features, int bits,
                     int32_t* qweight, gptq_stream_t stream);
 
+/* Grouped pack from weights -- serves pack_model / QuantGroupLinear for grouped runs (the reference packs every column
+ * against one per-row grid, quant.py:152-187, which is wrong for groupsize > 0).  Storage column j of output o holds the
+ * code of input column perm[j] (perm NULL: j), computed like quant.py:158 on the grid of group j / groupsize and clamped
+ * to [0, 2^bits - 1]:  code = clamp(round((weight[o][perm[j]] + zeros[g][o]) / scales[g][o])),  g = j / groupsize.
+ * scales / zeros fp32 [in/groupsize, out] (zeros = zero*scale); groupsize a positive multiple of 32 dividing in;
+ * perm int32 [in] or NULL.  perm = the solver's act-order permutation with dynamic groups (groups over consecutive
+ * positions of the permuted order): the act-order packed format of the functions below that take `perm`. */
+int gptq_pack_grouped(const void* weight, int w_dtype, int ldw, int out_features, int in_features,
+                      const float* scales, const float* zeros, int groupsize, const int32_t* perm, int bits,
+                      int32_t* qweight, gptq_stream_t stream);
+
 /* Packed -> dense weights: W[o][i] = scale[g][o] * (code - zero[g][o]), g = i / groupsize, tables
  * [in/groupsize, out] with `zero` the INTEGER zero point (quant.py:10 arithmetic); groupsize <= 0 means one
  * group.  Used to rebuild the Linears other ranks quantized and packed checkpoints. */
 int gptq_dequant_packed(const int32_t* qweight, const float* scale, const float* zero, int out_features,
                         int in_features, int bits, int groupsize, void* weight, int w_dtype, int ldw,
                         gptq_stream_t stream);
+/* The same for the act-order format (gptq_pack_grouped with perm): storage column j is written back to input column
+ * perm[j], on the grid of group j / groupsize; perm NULL = gptq_dequant_packed.  Serves dequant_packed(perm=...), which
+ * tests and tools use to compare a packed layer with its dense fake-quantized weight. */
+int gptq_dequant_packed_perm(const int32_t* qweight, const float* scale, const float* zero, const int32_t* perm,
+                             int out_features, int in_features, int bits, int groupsize, void* weight, int w_dtype,
+                             int ldw, gptq_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Packed dequant mat-vec -- replaces quant_cuda.vecquant3matmul /
@@ -262,6 +279,13 @@ int gptq_vecquant4matmul(const void* vec, int vec_dtype, const int32_t* mat, flo
 int gptq_vecquant_matmul_grouped(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
                                  const float* scales, const float* zeros, int height, int width,
                                  int bits, int groupsize, gptq_stream_t stream);
+/* The single-token forward of act-order QuantGroupLinear modules (format of gptq_pack_grouped with perm): packed row k
+ * multiplies vec[perm[k]] and uses the grid of group k / groupsize,
+ *   mul[col] += sum_k (scales[k/groupsize][col]*q[k,col] - zeros[k/groupsize][col]) * vec[perm[k]];
+ * perm int32 [in] (NULL = gptq_vecquant_matmul_grouped). */
+int gptq_vecquant_matmul_grouped_perm(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
+                                      const float* scales, const float* zeros, const int32_t* perm, int height,
+                                      int width, int bits, int groupsize, gptq_stream_t stream);
 
 /* Packed dequant GEMM -- the multi-token forward of the packed Linears (the reference's quant.py:188-197 only serves
  * one token):
@@ -277,6 +301,17 @@ int gptq_quant_gemm(const void* x, int x_dtype, int ldx, int M, const int32_t* q
                     const float* zeros, const float* bias, int K, int N, int bits, int groupsize, void* y, int y_dtype,
                     int ldy, void* workspace, size_t workspace_bytes, gptq_stream_t stream);
 size_t gptq_quant_gemm_workspace_bytes(int M, int K, int N, int bits, int groupsize);
+
+/* The multi-token forward of act-order QuantGroupLinear modules (format of gptq_pack_grouped with perm):
+ *   y[m][n] = sum_k x[m][perm[k]] * (scales[g][n]*q[k][n] - zeros[g][n]) (+ bias[n]),   g = k / groupsize,
+ * perm int32 [K], 16-byte aligned (NULL = gptq_quant_gemm), groupsize > 0; everything else as gptq_quant_gemm.  y is
+ * bit-identical to gptq_quant_gemm on a copy of x[:, perm] (same plan, same sums).  workspace: at least
+ * gptq_quant_gemm_perm_workspace_bytes(M, K, N, bits, groupsize) bytes, 16-byte aligned (large M gathers x there). */
+int gptq_quant_gemm_perm(const void* x, int x_dtype, int ldx, int M, const int32_t* qweight, const float* scales,
+                         const float* zeros, const int32_t* perm, const float* bias, int K, int N, int bits,
+                         int groupsize, void* y, int y_dtype, int ldy, void* workspace, size_t workspace_bytes,
+                         gptq_stream_t stream);
+size_t gptq_quant_gemm_perm_workspace_bytes(int M, int K, int N, int bits, int groupsize);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,18 @@
 """Packed dequant GEMM (gptq_amd.quant_matmul) against dense fp16 torch.nn.functional.linear on the Llama-7B Linears.
 
-    python tools/bench_qgemm.py [--iters 30] [--json out.json]
+    python tools/bench_qgemm.py [--iters 30] [--json out.json] [--perm]
 
 Shapes 4096->4096, 4096->11008, 11008->4096; M in {2, 8, 16, 64, 256, 2048}; 3-bit per-row and 4-bit g128 grids.  The
 two are timed alternately in one process with device events after a warm-up, each as a graph of 20 back-to-back
 calls (per-call host launch cost would otherwise set a ~20 us floor on both); reported: median time, TFLOP/s, GB/s of
 the packed weight bytes, and the share of the roof that bounds the case (2.5 PF fp16 MFMA, 8 TB/s HBM; the bytes
-counted are weights + activations + output)."""
+counted are weights + activations + output).
+
+--perm: the act-order format instead (4-bit g128, storage row k = input column perm[k], a random permutation): the
+grouped GEMM with perm (gptq_quant_gemm_perm) against the same GEMM without it on the same packed weights, M in
+{1, 4, 16, 128, 2048}, plus the grouped mat-vec with and without perm on the FC2 shape 36864 -> 9216.  Which gather the
+GEMM used (fused into the X staging, or a pre-pass into the workspace) is read off the workspace query.  With the
+diagnostic library (GPTQ_HIP_LIB=gptq_amd/libgptq_hip_diag.so) GPTQ_QG_PERM_FUSED_M moves the switch between the two."""
 import argparse
 import json
 import os
@@ -49,14 +55,97 @@ def timed(g, reps, rounds):
     return out
 
 
+def alternate(fa, fb, reps, warmup, iters):
+    """Median seconds per call of fa and fb, graphed and timed alternately."""
+    ga, gb = graphed(fa, reps), graphed(fb, reps)
+    for _ in range(warmup):
+        ga.replay(); gb.replay()
+    ta, tb = [], []
+    for _ in range(iters):
+        ta += timed(ga, reps, 1)
+        tb += timed(gb, reps, 1)
+    return statistics.median(ta), statistics.median(tb)
+
+
+PERM_MS = [1, 4, 16, 128, 2048]
+
+
+def main_perm(args):
+    import gptq_amd
+    from gptq_amd import _lib
+    from gptq_amd.quant import pack_codes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    bits, gs, reps = 4, 128, 20
+    rows = []
+
+    def grouped(K, N):
+        codes = torch.randint(0, 2 ** bits, (N, K), device=dev, generator=gen, dtype=torch.int32).to(torch.uint8)
+        s = torch.rand(K // gs, N, device=dev, generator=gen) * 0.01 + 1e-3
+        perm = torch.randperm(K, device=dev, generator=gen).to(torch.int32)
+        return pack_codes(codes, bits), s, s * 2 ** (bits - 1), perm
+
+    for K, N in SHAPES:
+        qw, s, z, perm = grouped(K, N)
+        for M in PERM_MS:
+            x = torch.randn(M, K, device=dev, generator=gen).half()
+            y0 = torch.empty(M, N, device=dev, dtype=torch.float16)
+            y1 = torch.empty(M, N, device=dev, dtype=torch.float16)
+            nb0 = lib.gptq_quant_gemm_workspace_bytes(M, K, N, bits, gs)
+            nb1 = lib.gptq_quant_gemm_perm_workspace_bytes(M, K, N, bits, gs)
+            ws0 = torch.empty(max(nb0, 1), dtype=torch.uint8, device=dev)
+            ws1 = torch.empty(max(nb1, 1), dtype=torch.uint8, device=dev)
+            plain = lambda: _lib.call("gptq_quant_gemm", x.data_ptr(), _lib.F16, K, M, qw.data_ptr(), s.data_ptr(),  # noqa: E731
+                                      z.data_ptr(), None, K, N, bits, gs, y0.data_ptr(), _lib.F16, N, ws0.data_ptr(), nb0,
+                                      _lib.stream(dev))
+            withp = lambda: _lib.call("gptq_quant_gemm_perm", x.data_ptr(), _lib.F16, K, M, qw.data_ptr(),  # noqa: E731
+                                      s.data_ptr(), z.data_ptr(), perm.data_ptr(), None, K, N, bits, gs, y1.data_ptr(),
+                                      _lib.F16, N, ws1.data_ptr(), nb1, _lib.stream(dev))
+            withp()
+            assert torch.equal(y1, gptq_amd.quant_matmul(x[:, perm.long()].contiguous(), qw, s, z, bits, gs))
+            t0, t1 = alternate(plain, withp, reps, args.warmup, args.iters)
+            gather = "prepass" if nb1 > nb0 else "fused"
+            r = dict(kind="gemm", K=K, N=N, M=M, bits=bits, groupsize=gs, gather=gather, noperm_us=t0 * 1e6,
+                     perm_us=t1 * 1e6, ratio=t1 / t0, target=1.10, met=t1 / t0 <= 1.10)
+            rows.append(r)
+            print(f"gemm {K:>5}->{N:<5} M={M:<5} no perm {r['noperm_us']:8.1f} us  perm ({gather:7}) {r['perm_us']:8.1f} us"
+                  f"  ratio {r['ratio']:5.3f}", flush=True)
+    K, N = 36864, 9216                                      # FC2 shape of the mat-vec
+    from gptq_amd import quant_cuda  # noqa: F401  (the wrapper's checks are not timed: the C entry points are)
+    qw, s, z, perm = grouped(K, N)
+    for xdt, code in ((torch.float16, _lib.F16), (torch.float32, _lib.F32)):
+        x = torch.randn(K, device=dev, generator=gen).to(xdt)
+        y = torch.zeros(N, device=dev)
+        h = qw.shape[0]
+        plain = lambda: _lib.call("gptq_vecquant_matmul_grouped", x.data_ptr(), code, qw.data_ptr(), y.data_ptr(),  # noqa: E731
+                                  s.data_ptr(), z.data_ptr(), h, N, bits, gs, _lib.stream(dev))
+        withp = lambda: _lib.call("gptq_vecquant_matmul_grouped_perm", x.data_ptr(), code, qw.data_ptr(),  # noqa: E731
+                                  y.data_ptr(), s.data_ptr(), z.data_ptr(), perm.data_ptr(), h, N, bits, gs,
+                                  _lib.stream(dev))
+        t0, t1 = alternate(plain, withp, reps, args.warmup, args.iters)
+        r = dict(kind="matvec", K=K, N=N, M=1, bits=bits, groupsize=gs, x_dtype=str(xdt).split(".")[-1],
+                 noperm_us=t0 * 1e6, perm_us=t1 * 1e6, ratio=t1 / t0, target=1.10, met=t1 / t0 <= 1.10)
+        rows.append(r)
+        print(f"matvec {K}->{N} x {r['x_dtype']}: no perm {r['noperm_us']:7.2f} us  perm {r['perm_us']:7.2f} us"
+              f"  ratio {r['ratio']:5.3f}", flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(dev), "library": _lib.LIB_PATH,
+                       "GPTQ_QG_PERM_FUSED_M": os.environ.get("GPTQ_QG_PERM_FUSED_M"), "rows": rows}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--perm", action="store_true", help="the act-order format: GEMM and mat-vec with / without perm")
     args = ap.parse_args()
     from gptq_amd.build import ensure_built
     ensure_built()
+    if args.perm:
+        return main_perm(args)
     import gptq_amd
     from gptq_amd import _lib
     from gptq_amd.quant import pack_codes
