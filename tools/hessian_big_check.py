@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Correctness + speed of the Hessian kernels through the C ABI (gptq_hessian_accum_group).
-    GPTQ_HESS_BIG=0|1|2 python3 tools/hessian_big_check.py [--dump path] [--no-time]
+    GPTQ_HESS_BIG=0|1|2 python3 tools/hessian_big_check.py [--dump path] [--no-time] | --exact [--n-cu N]
 Writes H (C = 1024, 2 problems) to `--dump` so two builds / settings can be compared bit for bit."""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if "--exact" in sys.argv[1:]:      # the bit-exact sweep of tests/hessian_ref.py under the same environment ([--n-cu N])
+    import runpy
+    _ref = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "hessian_ref.py")
+    sys.argv = [_ref, "--exact-sweep"] + [a for a in sys.argv[1:] if a != "--exact"]
+    runpy.run_path(_ref, run_name="__main__")
+    sys.exit(0)
 import torch
 from gptq_amd import _lib
 
