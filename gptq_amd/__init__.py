@@ -5,7 +5,8 @@ call does, and fails loudly if the library was not built (`python -m gptq_amd.bu
 """
 from .gptq import GPTQ, fasterquant_many, flush_pending  # noqa: F401
 from .modelutils import DEV, find_layers  # noqa: F401
-from .quant import (Quant3Linear, Quant4Linear, QuantGroupLinear, Quantizer, make_quant3,  # noqa: F401
-                    make_quant4, pack_codes, pack_grouped, quant_matmul, quantize, set_multi_token)
+from .quant import (Quant2Linear, Quant3Linear, Quant4Linear, Quant8Linear, QuantGroupLinear,  # noqa: F401
+                    Quantizer, make_quant2, make_quant3, make_quant4, make_quant8, pack_codes, pack_grouped,
+                    quant_matmul, quantize, set_multi_token)
 
 __version__ = "0.1.0"

@@ -53,6 +53,8 @@ _SIGNATURES = {
     "gptq_dequant_packed_perm": (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p]),
     "gptq_vecquant3matmul": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _i, _p]),
     "gptq_vecquant4matmul": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _i, _p]),
+    "gptq_vecquant2matmul": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _i, _p]),
+    "gptq_vecquant8matmul": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _i, _p]),
     "gptq_vecquant_matmul_grouped": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "gptq_vecquant_matmul_grouped_perm": (C.c_int, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "gptq_quant_gemm": (C.c_int, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _z, _p]),

@@ -1,4 +1,4 @@
-// Packed 3/4-bit dequant mat-vec  mul[col] += sum_k (scale[col]*q[k,col] - zero[col]) * vec[k]
+// Packed 2/3/4/8-bit dequant mat-vec  mul[col] += sum_k (scale[col]*q[k,col] - zero[col]) * vec[k]
 // (replaces quant_cuda.vecquant3matmul / _faster, quant_cuda_kernel.cu:88-244).
 //
 // HBM-bound: every packed word is read exactly once.  Design for gfx950:
@@ -36,7 +36,8 @@ __device__ __forceinline__ void dot_group(const uint32_t (&w)[BITS], const float
   } else {
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
-      const uint32_t v = (w[j >> 3] >> (4 * (j & 7))) & 15u;
+      constexpr int CPW = 32 / BITS;                  // 2 / 4 / 8 bits: code j of a word at bit BITS * j
+      const uint32_t v = (w[j / CPW] >> (BITS * (j % CPW))) & ((1u << BITS) - 1);
       acc = fmaf((float)v, x[j], acc);
     }
   }
@@ -179,6 +180,14 @@ __global__ __launch_bounds__(256) void matvec_kernel(const TV* __restrict__ vec,
 // weight, but no faster than the old kernel: dot2 issues at a quarter of the fma rate.)
 // Windows: 3-bit pairs (j, j+5) [15 bits apart] for j in 0..4 and 10..14, (j, j+6) [18 bits] for j in 20..25 -- together
 // all 32 codes of a 96-bit group; 4-bit pairs are nibbles (k, k+4) of one word.
+// 2 and 8 bits: the decode holds a code of BITS bits at bit p of the 10-bit mantissa only for p <= 10 - BITS, so the
+// windows shift the codes there.  2-bit pairs are codes (k, k+8) of one word, both at bit 2k of their halves, moved to
+// bit 8 (window = stream from bit 32 word + 2k - 8): constant part 1024 * 2^-8 = 4 per unit of x.  8-bit pairs are bytes
+// (k, k+2) of one word, both at bit 8k of their halves, moved to bit 2 (window from bit 32 word + 8k - 2): 1024 + 4c, exact
+// up to c = 255, constant part 256 per unit of x -- the same order as the codes themselves, like the other widths.
+// (Not measured against it: a v_perm_b32 that builds both halves 0x64cc = 1024 + c in one instruction, saving the
+// window shift at four times the constant part.  8 bits move twice the bytes per weight of 4 bits at the same number of
+// decode instructions per weight, so the decode is further from binding it than at any other width.)
 // ---------------------------------------------------------------------------------------------
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 
@@ -195,7 +204,19 @@ __host__ __device__ constexpr PairSlot pair4(int t) {
   const int word = t >> 2, k = t & 3;
   return PairSlot{8 * word + k, 8 * word + k + 4, 6, 6, 32 * word + 4 * k - 6};
 }
-template <int BITS> __host__ __device__ constexpr PairSlot pair_slot(int t) { return BITS == 3 ? pair3(t) : pair4(t); }
+__host__ __device__ constexpr PairSlot pair2(int t) {
+  // t in [0, 16): word t / 8, codes (k, k + 8), both at bit 8 of their halves: window = stream from bit 32 word + 2k - 8
+  const int word = t >> 3, k = t & 7;
+  return PairSlot{16 * word + k, 16 * word + k + 8, 8, 8, 32 * word + 2 * k - 8};
+}
+__host__ __device__ constexpr PairSlot pair8(int t) {
+  // t in [0, 16): word t / 2, bytes (k, k + 2), both at bit 2 of their halves: window = stream from bit 32 word + 8k - 2
+  const int word = t >> 1, k = t & 1;
+  return PairSlot{4 * word + k, 4 * word + k + 2, 2, 2, 32 * word + 8 * k - 2};
+}
+template <int BITS> __host__ __device__ constexpr PairSlot pair_slot(int t) {
+  return BITS == 3 ? pair3(t) : BITS == 4 ? pair4(t) : BITS == 2 ? pair2(t) : pair8(t);
+}
 // the same table computed per lane while x is staged (a select cascade over the 16 constexpr entries costs ~100 vector
 // instructions per wave, 15 % of the kernel): codes and bit positions only, checked against the table at compile time
 template <int BITS> __host__ __device__ constexpr PairSlot pair_slot_rt(int t) {
@@ -203,6 +224,14 @@ template <int BITS> __host__ __device__ constexpr PairSlot pair_slot_rt(int t) {
     const bool c = t >= 10;
     const int j = t + (t >= 5 ? 5 : 0) + (c ? 5 : 0);
     return PairSlot{j, j + (c ? 6 : 5), c ? 5 : 7, c ? 7 : 6, 0};
+  }
+  if (BITS == 2) {
+    const int j = 16 * (t >> 3) + (t & 7);
+    return PairSlot{j, j + 8, 8, 8, 0};
+  }
+  if (BITS == 8) {
+    const int j = 4 * (t >> 1) + (t & 1);
+    return PairSlot{j, j + 2, 2, 2, 0};
   }
   const int j = 8 * (t >> 2) + (t & 3);
   return PairSlot{j, j + 4, 6, 6, 0};
@@ -214,7 +243,21 @@ template <int BITS> constexpr bool pair_slot_rt_ok() {
   }
   return true;
 }
-static_assert(pair_slot_rt_ok<3>() && pair_slot_rt_ok<4>(), "pair_slot_rt disagrees with the pair table");
+static_assert(pair_slot_rt_ok<3>() && pair_slot_rt_ok<4>() && pair_slot_rt_ok<2>() && pair_slot_rt_ok<8>(),
+              "pair_slot_rt disagrees with the pair table");
+// every code of a 32-group sits in exactly one slot, inside the mantissa, and the window puts it where the table says
+template <int BITS> constexpr bool pair_table_ok() {
+  unsigned seen = 0;
+  for (int t = 0; t < 16; ++t) {
+    const PairSlot ps = pair_slot<BITS>(t);
+    if (ps.plo + BITS > 10 || ps.phi + BITS > 10 || ps.plo < 0 || ps.phi < 0) return false;
+    if (BITS * ps.jlo - ps.s != ps.plo || BITS * ps.jhi - ps.s != 16 + ps.phi) return false;
+    if ((seen >> ps.jlo & 1u) || (seen >> ps.jhi & 1u) || ps.jlo == ps.jhi) return false;
+    seen |= (1u << ps.jlo) | (1u << ps.jhi);
+  }
+  return seen == 0xffffffffu;
+}
+static_assert(pair_table_ok<2>() && pair_table_ok<3>() && pair_table_ok<4>() && pair_table_ok<8>(), "bad pair table");
 
 // sum over the 16 lanes of a DPP row, result in every lane (row rotations: no LDS round trips)
 __device__ __forceinline__ float row16_sum(float v) {
@@ -463,12 +506,32 @@ extern "C" int gptq_vecquant4matmul(const void* vec, int vec_dtype, const int32_
                           static_cast<hipStream_t>(stream), "gptq_vecquant4matmul");
 }
 
+extern "C" int gptq_vecquant2matmul(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
+                                    const float* scales, const float* zeros, int height, int width,
+                                    gptq_stream_t stream) {
+  return launch_matvec<2>(vec, vec_dtype, mat, mul, scales, zeros, height, width, 0,
+                          static_cast<hipStream_t>(stream), "gptq_vecquant2matmul");
+}
+
+extern "C" int gptq_vecquant8matmul(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
+                                    const float* scales, const float* zeros, int height, int width,
+                                    gptq_stream_t stream) {
+  return launch_matvec<8>(vec, vec_dtype, mat, mul, scales, zeros, height, width, 0,
+                          static_cast<hipStream_t>(stream), "gptq_vecquant8matmul");
+}
+
 extern "C" int gptq_vecquant_matmul_grouped(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
                                             const float* scales, const float* zeros, int height, int width,
                                             int bits, int groupsize, gptq_stream_t stream) {
-  GPTQ_CHECK_ARG(bits == 3 || bits == 4, "gptq_vecquant_matmul_grouped: bits must be 3 or 4");
+  GPTQ_CHECK_ARG(bits == 2 || bits == 3 || bits == 4 || bits == 8, "gptq_vecquant_matmul_grouped: bits must be 2, 3, 4 or 8");
   GPTQ_CHECK_ARG(groupsize > 0, "gptq_vecquant_matmul_grouped: groupsize must be positive");
   GPTQ_CHECK_ARG((height / bits * 32) % groupsize == 0, "gptq_vecquant_matmul_grouped: in_features must be a multiple of groupsize");
+  if (bits == 2)
+    return launch_matvec<2>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
+                            static_cast<hipStream_t>(stream), "gptq_vecquant_matmul_grouped");
+  if (bits == 8)
+    return launch_matvec<8>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
+                            static_cast<hipStream_t>(stream), "gptq_vecquant_matmul_grouped");
   if (bits == 3)
     return launch_matvec<3>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
                             static_cast<hipStream_t>(stream), "gptq_vecquant_matmul_grouped");
@@ -480,9 +543,15 @@ extern "C" int gptq_vecquant_matmul_grouped_perm(const void* vec, int vec_dtype,
                                                  const float* scales, const float* zeros, const int32_t* perm,
                                                  int height, int width, int bits, int groupsize, gptq_stream_t stream) {
   const char* who = "gptq_vecquant_matmul_grouped_perm";
-  GPTQ_CHECK_ARG(bits == 3 || bits == 4, "%s: bits must be 3 or 4", who);
+  GPTQ_CHECK_ARG(bits == 2 || bits == 3 || bits == 4 || bits == 8, "%s: bits must be 2, 3, 4 or 8", who);
   GPTQ_CHECK_ARG(groupsize > 0, "%s: groupsize must be positive", who);
   GPTQ_CHECK_ARG((height / bits * 32) % groupsize == 0, "%s: in_features must be a multiple of groupsize", who);
+  if (bits == 2)
+    return launch_matvec<2>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
+                            static_cast<hipStream_t>(stream), who, perm);
+  if (bits == 8)
+    return launch_matvec<8>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
+                            static_cast<hipStream_t>(stream), who, perm);
   if (bits == 3)
     return launch_matvec<3>(vec, vec_dtype, mat, mul, scales, zeros, height, width, groupsize,
                             static_cast<hipStream_t>(stream), who, perm);

@@ -1,9 +1,10 @@
-// int3 / int4 bit packing on the GPU  (replaces Quant3Linear.pack, quant.py:152-187 -- a host
+// int2 / int3 / int4 / int8 bit packing on the GPU  (replaces Quant3Linear.pack, quant.py:152-187 -- a host
 // numpy loop the reference itself marks "TODO: perform packing on GPU", opt.py:361 -- and the
 // int4 layout of zeroShot/models/quant.py:176-185).  HBM-bound: reads the [out, in] weights once
 // (coalesced along `in`), transposes 64 x 128 tiles of integer codes through LDS, and writes the
 // [in/32*bits, out] words coalesced along `out`.  Bit-exact, including the reference's uint32
-// wrap-around for out-of-range codes.
+// wrap-around for out-of-range codes.  2 and 8 bits follow the int4 rule with 16 or 4 codes per word: code i of a
+// column sits in word i / (32/bits) at bit bits * (i % (32/bits)).
 #include "common.h"
 
 namespace gptq {
@@ -31,6 +32,20 @@ __device__ __forceinline__ void pack3_words(const uint32_t* v, int stride, uint3
 #pragma unroll
   for (int j = 0; j < 10; ++j) w2 |= v[(22 + j) * stride] << (3 * j + 2);
   out[0] = w0; out[1] = w1; out[2] = w2;
+}
+
+// 32 codes -> BITS words of 32 / BITS codes each (BITS = 2, 4, 8): code j of a word at bit BITS * j, OR-ed unmasked like
+// zeroShot/models/quant.py:185, so an out-of-range code spills into its neighbours exactly as it does at 4 bits.
+template <int BITS, typename V>
+__device__ __forceinline__ void pack_pow2_words(const V* v, int32_t* __restrict__ qweight, long gi, int n_out, int o) {
+  constexpr int CPW = 32 / BITS;
+#pragma unroll
+  for (int k = 0; k < BITS; ++k) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < CPW; ++j) w |= (uint32_t)v[CPW * k + j] << (BITS * j);
+    qweight[(gi * BITS + k) * n_out + o] = (int32_t)w;
+  }
 }
 
 // SRC = 0: weights (T) + per-row scale / zero*scale -> codes;  SRC = 1: ready uint8 codes.
@@ -86,13 +101,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const T* __restrict__ src, in
 #pragma unroll
     for (int k = 0; k < 3; ++k) qweight[((long)gi * 3 + k) * n_out + o] = (int32_t)w[k];
   } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                // zeroShot/models/quant.py:185
-      uint32_t w = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w |= v[8 * k + j] << (4 * j);
-      qweight[((long)gi * 4 + k) * n_out + o] = (int32_t)w;
-    }
+    pack_pow2_words<BITS>(v, qweight, gi, n_out, o);   // zeroShot/models/quant.py:185
   }
 }
 
@@ -139,16 +148,27 @@ __global__ __launch_bounds__(256) void pack_codes_wide_kernel(const uint8_t* __r
 #pragma unroll
       for (int k = 0; k < 3; ++k) qweight[((long)gi * 3 + k) * n_out + o] = (int32_t)w[k];
     } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) w |= c[8 * k + j] << (4 * j);
-        qweight[((long)gi * 4 + k) * n_out + o] = (int32_t)w;
-      }
+      pack_pow2_words<BITS>(c, qweight, gi, n_out, o);
     }
   }
 }
+
+// one launch per packed width (the callers have checked `bits`)
+#define GPTQ_PACK_BITS(bits, GO)                                                                                    \
+  do {                                                                                                              \
+    if ((bits) == 2) GO(2);                                                                                         \
+    else if ((bits) == 3) GO(3);                                                                                    \
+    else if ((bits) == 8) GO(8);                                                                                    \
+    else GO(4);                                                                                                     \
+  } while (0)
+
+// (DQ / PG below are defined next to each launch; these bind the weight type)
+#define DQ_FLOAT(B) DQ(float, B)
+#define DQ_HALF(B) DQ(__half, B)
+#define DQ_HIP_BFLOAT16(B) DQ(__hip_bfloat16, B)
+#define PG_FLOAT(B) PG(float, B)
+#define PG_HALF(B) PG(__half, B)
+#define PG_HIP_BFLOAT16(B) PG(__hip_bfloat16, B)
 
 template <typename T, int SRC>
 static int launch_pack(const T* src, int ld, int n_out, int n_in, const float* scales, const float* zeros,
@@ -156,8 +176,9 @@ static int launch_pack(const T* src, int ld, int n_out, int n_in, const float* s
   const dim3 grid(cdiv(n_in, PT_I), cdiv(n_out, PT_O));
   // uint8 codes: 32-bit loads when every row starts 4-byte aligned
   const bool vec4 = SRC == 1 && ld % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 4 == 0;
-  if (bits == 3) pack_kernel<T, 3, SRC><<<grid, 256, 0, s>>>(src, ld, n_out, n_in, scales, zeros, qweight, vec4);
-  else pack_kernel<T, 4, SRC><<<grid, 256, 0, s>>>(src, ld, n_out, n_in, scales, zeros, qweight, vec4);
+#define PK(B) pack_kernel<T, B, SRC><<<grid, 256, 0, s>>>(src, ld, n_out, n_in, scales, zeros, qweight, vec4)
+  GPTQ_PACK_BITS(bits, PK);
+#undef PK
   GPTQ_CHECK_LAUNCH("pack_kernel");
   return GPTQ_OK;
 }
@@ -212,13 +233,7 @@ __global__ __launch_bounds__(256) void pack_grouped_kernel(const T* __restrict__
 #pragma unroll
     for (int k = 0; k < 3; ++k) qweight[((long)gi * 3 + k) * n_out + o] = (int32_t)w[k];
   } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      uint32_t w = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w |= v[8 * k + j] << (4 * j);
-      qweight[((long)gi * 4 + k) * n_out + o] = (int32_t)w;
-    }
+    pack_pow2_words<BITS>(v, qweight, gi, n_out, o);
   }
 }
 
@@ -248,12 +263,14 @@ __global__ __launch_bounds__(256) void dequant_kernel(const int32_t* __restrict_
       const int bit = 3 * j, word = bit >> 5, off = bit & 31;
       v = (off <= 29) ? (w[word] >> off) & 7u : __builtin_amdgcn_alignbit(w[(word + 1) % BITS], w[word], off) & 7u;
     } else {
-      v = (w[j >> 3] >> (4 * (j & 7))) & 15u;
+      constexpr int CPW = 32 / BITS;
+      v = (w[j / CPW] >> (BITS * (j % CPW))) & ((1u << BITS) - 1);
     }
     float q = s * ((float)v - z);
     // round to fp32 first, like the solver: without this the scatter variant folds the product and the conversion to a
     // 16-bit type into one v_fma_mixlo (a single rounding), one ulp off the fake-quantized weight at rare ties
-    if constexpr (PERM && sizeof(T) == 2) asm volatile("" : "+v"(q));
+    // (2 and 8 bits pin it in the plain variant too: the same rule whatever the compiler makes of the shorter decode)
+    if constexpr (sizeof(T) == 2 && (PERM || BITS == 2 || BITS == 8)) asm volatile("" : "+v"(q));
     T* d = PERM ? row + perm[gi * 32 + j] : dst + j;
     if (PERM && (unsigned)perm[gi * 32 + j] >= (unsigned)n_in) continue;   // never a stray write
     if constexpr (sizeof(T) == 4) *d = q;
@@ -266,7 +283,7 @@ __global__ __launch_bounds__(256) void dequant_kernel(const int32_t* __restrict_
 using namespace gptq;
 
 static int check_pack_shape(const char* who, int out_features, int in_features, int bits) {
-  GPTQ_CHECK_ARG(bits == 3 || bits == 4, "%s: bits must be 3 or 4", who);
+  GPTQ_CHECK_ARG(bits == 2 || bits == 3 || bits == 4 || bits == 8, "%s: bits must be 2, 3, 4 or 8", who);
   GPTQ_CHECK_ARG(out_features > 0 && in_features > 0, "%s: bad sizes", who);
   GPTQ_CHECK_ARG(in_features % 32 == 0, "%s: in_features must be a multiple of 32", who);
   return GPTQ_OK;
@@ -298,8 +315,9 @@ extern "C" int gptq_pack_codes(const uint8_t* codes, int ldc, int out_features, 
   if (ldc % 16 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0) {
     const dim3 grid(cdiv(in_features, PW_I), cdiv(out_features, PW_O));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (bits == 3) pack_codes_wide_kernel<3><<<grid, 256, 0, s>>>(codes, ldc, out_features, in_features, qweight);
-    else pack_codes_wide_kernel<4><<<grid, 256, 0, s>>>(codes, ldc, out_features, in_features, qweight);
+#define PW(B) pack_codes_wide_kernel<B><<<grid, 256, 0, s>>>(codes, ldc, out_features, in_features, qweight)
+    GPTQ_PACK_BITS(bits, PW);
+#undef PW
     GPTQ_CHECK_LAUNCH("pack_codes_wide_kernel");
     return GPTQ_OK;
   }
@@ -318,9 +336,9 @@ extern "C" int gptq_dequant_packed(const int32_t* qweight, const float* scale, c
   const dim3 grid(cdiv(out_features, 64), cdiv(in_features / 32, 4));
   hipStream_t s = static_cast<hipStream_t>(stream);
 #define DQ(T, B) dequant_kernel<T, B><<<grid, 256, 0, s>>>(qweight, scale, zero, out_features, in_features, groupsize, static_cast<T*>(weight), ldw)
-  if (w_dtype == GPTQ_F32) { if (bits == 3) DQ(float, 3); else DQ(float, 4); }
-  else if (w_dtype == GPTQ_F16) { if (bits == 3) DQ(__half, 3); else DQ(__half, 4); }
-  else if (w_dtype == GPTQ_BF16) { if (bits == 3) DQ(__hip_bfloat16, 3); else DQ(__hip_bfloat16, 4); }
+  if (w_dtype == GPTQ_F32) { GPTQ_PACK_BITS(bits, DQ_FLOAT); }
+  else if (w_dtype == GPTQ_F16) { GPTQ_PACK_BITS(bits, DQ_HALF); }
+  else if (w_dtype == GPTQ_BF16) { GPTQ_PACK_BITS(bits, DQ_HIP_BFLOAT16); }
   else GPTQ_CHECK_ARG(false, "gptq_dequant_packed: unknown dtype %d", w_dtype);
 #undef DQ
   GPTQ_CHECK_LAUNCH("dequant_kernel");
@@ -340,9 +358,9 @@ extern "C" int gptq_pack_grouped(const void* weight, int w_dtype, int ldw, int o
 #define PG(T, B)                                                                                                    \
   pack_grouped_kernel<T, B><<<grid, 256, 0, s>>>(static_cast<const T*>(weight), ldw, out_features, in_features, scales, \
                                                  zeros, groupsize, perm, qweight)
-  if (w_dtype == GPTQ_F32) { if (bits == 3) PG(float, 3); else PG(float, 4); }
-  else if (w_dtype == GPTQ_F16) { if (bits == 3) PG(__half, 3); else PG(__half, 4); }
-  else if (w_dtype == GPTQ_BF16) { if (bits == 3) PG(__hip_bfloat16, 3); else PG(__hip_bfloat16, 4); }
+  if (w_dtype == GPTQ_F32) { GPTQ_PACK_BITS(bits, PG_FLOAT); }
+  else if (w_dtype == GPTQ_F16) { GPTQ_PACK_BITS(bits, PG_HALF); }
+  else if (w_dtype == GPTQ_BF16) { GPTQ_PACK_BITS(bits, PG_HIP_BFLOAT16); }
   else GPTQ_CHECK_ARG(false, "gptq_pack_grouped: unknown dtype %d", w_dtype);
 #undef PG
   GPTQ_CHECK_LAUNCH("pack_grouped_kernel");
@@ -365,9 +383,9 @@ extern "C" int gptq_dequant_packed_perm(const int32_t* qweight, const float* sca
 #define DQ(T, B)                                                                                                    \
   dequant_kernel<T, B, true><<<grid, 256, 0, s>>>(qweight, scale, zero, out_features, in_features, groupsize,       \
                                                   static_cast<T*>(weight), ldw, perm)
-  if (w_dtype == GPTQ_F32) { if (bits == 3) DQ(float, 3); else DQ(float, 4); }
-  else if (w_dtype == GPTQ_F16) { if (bits == 3) DQ(__half, 3); else DQ(__half, 4); }
-  else if (w_dtype == GPTQ_BF16) { if (bits == 3) DQ(__hip_bfloat16, 3); else DQ(__hip_bfloat16, 4); }
+  if (w_dtype == GPTQ_F32) { GPTQ_PACK_BITS(bits, DQ_FLOAT); }
+  else if (w_dtype == GPTQ_F16) { GPTQ_PACK_BITS(bits, DQ_HALF); }
+  else if (w_dtype == GPTQ_BF16) { GPTQ_PACK_BITS(bits, DQ_HIP_BFLOAT16); }
   else GPTQ_CHECK_ARG(false, "gptq_dequant_packed_perm: unknown dtype %d", w_dtype);
 #undef DQ
   GPTQ_CHECK_LAUNCH("dequant_kernel");

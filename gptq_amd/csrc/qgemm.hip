@@ -1,8 +1,8 @@
-// Packed 3/4-bit dequant GEMM  Y[M, N] = X[M, K] . Wdeq[K, N] (+ bias[N]),  Wdeq[k][n] = scale[g][n]*q[k][n] - zeros[g][n]
+// Packed 2/3/4/8-bit dequant GEMM  Y[M, N] = X[M, K] . Wdeq[K, N] (+ bias[N]),  Wdeq[k][n] = scale[g][n]*q[k][n] - zeros[g][n]
 // (multi-token forward of the packed Linears; the single-token case stays on matvec.hip).
 //
 // Arithmetic contract (the mat-vec's, hoisted the same way):
-//   * the MFMAs run on the exact integer codes (0..15 are exact in fp16 and bf16) against fp16/bf16 activations, so every
+//   * the MFMAs run on the exact integer codes (0..255 are exact in fp16 and bf16) against fp16/bf16 activations, so every
 //     product is exact and the k-sum is an fp32 chain;
 //   * the grid is applied in fp32 once per group of K (per-row grids: once per K chunk):
 //       y += s[g][n] * sum_{k in g}(q x) - z[g][n] * sum_{k in g}(x),
@@ -11,7 +11,8 @@
 //
 // Tiling (v_mfma_f32_16x16x32_{f16,bf16}; lane l holds A[l&15][8(l>>4)+j] and B[8(l>>4)+j][l&15], j = 0..7):
 //   * one B fragment of a lane is 8 consecutive k of one column: 4-bit = exactly one packed word, 3-bit = a 24-bit window
-//     of the 96-bit group stream, at most two words (alignbit);
+//     of the 96-bit group stream, at most two words (alignbit), 2-bit = one 16-bit half of a word, 8-bit = two whole
+//     words;
 //   * a wave owns MSUB x 4 output tiles of 16 x 16: MSUB*16 rows, 64 columns.  Its lane (l&15) holds the 4 ADJACENT
 //     columns 4(l&15) + t of the four column tiles t, so the packed words of a step arrive as one 16-byte load per lane;
 //   * a workgroup is 4 waves, WM along M and 4/WM along N; the X tile (BM rows x 128 k) is staged through LDS with the
@@ -68,24 +69,38 @@ template <int BITS, typename XT> __device__ __forceinline__ typename QgFrag<XT>:
   for (int j = 0; j < 8; ++j) f[j] = (typename QgFrag<XT>::elem)(float)((win >> (BITS * j)) & ((1u << BITS) - 1));
   return f;
 }
+// 8-bit: the fragment is two whole words, bytes 0..3 of `lo` then of `hi`
+template <typename XT> __device__ __forceinline__ typename QgFrag<XT>::type qg_decode_bytes(uint32_t lo, uint32_t hi) {
+  typename QgFrag<XT>::type f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[j] = (typename QgFrag<XT>::elem)(float)((lo >> (8 * j)) & 0xffu);
+    f[4 + j] = (typename QgFrag<XT>::elem)(float)((hi >> (8 * j)) & 0xffu);
+  }
+  return f;
+}
 
 template <typename YT> __device__ __forceinline__ void qg_store(YT* p, float v);
 template <> __device__ __forceinline__ void qg_store<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void qg_store<__half>(__half* p, float v) { *p = __float2half(v); }
 template <> __device__ __forceinline__ void qg_store<__hip_bfloat16>(__hip_bfloat16* p, float v) { *p = __float2bfloat16(v); }
 
-// The packed words of one k-step for the lane's 4 columns: w[0] (4-bit), w[0] / w[1] = low / high word of the 24-bit
-// window (3-bit).  Columns at or past N read as 0 (their outputs are never stored).
-template <int BITS> struct QgWords { uint4 w[BITS == 3 ? 2 : 1]; };
+// The packed words of one k-step for the lane's 4 columns: w[0] (4-bit, and 2-bit: the word that holds the lane's 16-bit
+// half), w[0] / w[1] = low / high word of the 24-bit window (3-bit) or of the fragment's 8 bytes (8-bit).  Columns at or
+// past N read as 0 (their outputs are never stored).
+template <int BITS> constexpr int qg_nwords() { return BITS == 3 || BITS == 8 ? 2 : 1; }
+template <int BITS> struct QgWords { uint4 w[qg_nwords<BITS>()]; };
 
 template <int BITS>
 __device__ __forceinline__ void qg_load_words(QgWords<BITS>& out, const int32_t* __restrict__ qw, int ks, int col, int N,
                                               bool wvec, int h) {
-  constexpr int NW = BITS == 3 ? 2 : 1;
+  constexpr int NW = qg_nwords<BITS>();
 #pragma unroll
   for (int i = 0; i < NW; ++i) {
-    // 4-bit: word h of the group; 3-bit: words (24h) / 32 and (24h + 23) / 32 of the group's three
-    const int r = BITS == 4 ? h : (i == 0 ? (24 * h) >> 5 : (24 * h + 23) >> 5);
+    // 4-bit: word h of the group; 3-bit: words (24h) / 32 and (24h + 23) / 32 of the group's three; 2-bit: word h / 2 of
+    // the group's two; 8-bit: words 2h and 2h + 1 of the group's eight
+    const int r = BITS == 4 ? h : BITS == 2 ? h >> 1 : BITS == 8 ? 2 * h + i
+                                                                 : (i == 0 ? (24 * h) >> 5 : (24 * h + 23) >> 5);
     const int32_t* p = qw + (size_t)(ks * BITS + r) * N + col;
     if (wvec && col + 3 < N) {
       out.w[i] = *reinterpret_cast<const uint4*>(p);
@@ -101,8 +116,21 @@ __device__ __forceinline__ void qg_load_words(QgWords<BITS>& out, const int32_t*
 template <int BITS> __device__ __forceinline__ uint32_t qg_window(const QgWords<BITS>& w, int t, int h) {
   const uint32_t lo = t == 0 ? w.w[0].x : t == 1 ? w.w[0].y : t == 2 ? w.w[0].z : w.w[0].w;
   if (BITS == 4) return lo;
+  if (BITS == 2) return lo >> (16 * (h & 1));            // (the decode masks the 8 codes out of the low 16 bits)
   const uint32_t hi = t == 0 ? w.w[BITS == 3].x : t == 1 ? w.w[BITS == 3].y : t == 2 ? w.w[BITS == 3].z : w.w[BITS == 3].w;
   return __builtin_amdgcn_alignbit(hi, lo, (24 * h) & 31);
+}
+
+// the lane's B fragment of column tile t: 8 consecutive k of one column as exact fp16 / bf16 values
+template <int BITS, typename XT>
+__device__ __forceinline__ typename QgFrag<XT>::type qg_fragment(const QgWords<BITS>& w, int t, int h) {
+  if constexpr (BITS == 8) {
+    const uint32_t lo = t == 0 ? w.w[0].x : t == 1 ? w.w[0].y : t == 2 ? w.w[0].z : w.w[0].w;
+    const uint32_t hi = t == 0 ? w.w[1].x : t == 1 ? w.w[1].y : t == 2 ? w.w[1].z : w.w[1].w;
+    return qg_decode_bytes<XT>(lo, hi);
+  } else {
+    return qg_decode<BITS, XT>(qg_window<BITS>(w, t, h));
+  }
 }
 
 // Grid: (column tiles, row tiles, K chunks).  Block: 256 threads.  `part` != nullptr: write the chunk's partial sums
@@ -220,7 +248,7 @@ __global__ __launch_bounds__(256) void qgemm_kernel(const XT* __restrict__ x, in
       if (ks < kend) {                                     // workgroup-uniform
         F b[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) b[t] = qg_decode<BITS, XT>(qg_window<BITS>(wcur[s], t, h));
+        for (int t = 0; t < 4; ++t) b[t] = qg_fragment<BITS, XT>(wcur[s], t, h);
 #pragma unroll
         for (int i = 0; i < MSUB; ++i) {
           const int r0 = wm * MSUB * 16 + 16 * i;
@@ -420,7 +448,7 @@ using namespace gptq;
 
 extern "C" size_t gptq_quant_gemm_workspace_bytes(int M, int K, int N, int bits, int groupsize) {
   (void)groupsize;
-  if (M <= 0 || N <= 0 || K <= 0 || K % 32 || (bits != 3 && bits != 4)) return 0;
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32 || (bits != 2 && bits != 3 && bits != 4 && bits != 8)) return 0;
   return qg_workspace_bytes(qg_plan(M, K, N, bits), M, N);
 }
 
@@ -429,7 +457,7 @@ static int quant_gemm_impl(const char* who, const void* x, int x_dtype, int ldx,
                            int bits, int groupsize, void* y, int y_dtype, int ldy, void* workspace,
                            size_t workspace_bytes, hipStream_t s) {
   GPTQ_CHECK_ARG(x && qweight && scales && zeros && y, "%s: null pointer", who);
-  GPTQ_CHECK_ARG(bits == 3 || bits == 4, "%s: bits must be 3 or 4", who);
+  GPTQ_CHECK_ARG(bits == 2 || bits == 3 || bits == 4 || bits == 8, "%s: bits must be 2, 3, 4 or 8", who);
   GPTQ_CHECK_ARG(M >= 1 && N >= 1 && K >= 32 && K % 32 == 0, "%s: need M >= 1, N >= 1 and K a positive multiple of 32", who);
   GPTQ_CHECK_ARG(x_dtype == GPTQ_F16 || x_dtype == GPTQ_BF16, "%s: x must be fp16 or bf16", who);
   GPTQ_CHECK_ARG(y_dtype == GPTQ_F32 || y_dtype == GPTQ_F16 || y_dtype == GPTQ_BF16, "%s: y must be fp32, fp16 or bf16", who);
@@ -458,13 +486,19 @@ static int quant_gemm_impl(const char* who, const void* x, int x_dtype, int ldx,
   const bool xvec = reinterpret_cast<uintptr_t>(x) % 16 == 0 && ldx % 8 == 0;
   const bool wvec = reinterpret_cast<uintptr_t>(qweight) % 16 == 0 && N % 4 == 0;
   const int gs = groupsize > 0 ? groupsize : 0;
+#define QG_Y(B, XT) qg_launch_y<B, XT>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm)
   if (x_dtype == GPTQ_F16) {
-    if (bits == 3) qg_launch_y<3, __half>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm);
-    else qg_launch_y<4, __half>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm);
+    if (bits == 2) QG_Y(2, __half);
+    else if (bits == 3) QG_Y(3, __half);
+    else if (bits == 8) QG_Y(8, __half);
+    else QG_Y(4, __half);
   } else {
-    if (bits == 3) qg_launch_y<3, __hip_bfloat16>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm);
-    else qg_launch_y<4, __hip_bfloat16>(y_dtype, p, x, ldx, M, qweight, scales, zeros, bias, K, N, gs, y, ldy, part, xvec, wvec, s, perm);
+    if (bits == 2) QG_Y(2, __hip_bfloat16);
+    else if (bits == 3) QG_Y(3, __hip_bfloat16);
+    else if (bits == 8) QG_Y(8, __hip_bfloat16);
+    else QG_Y(4, __hip_bfloat16);
   }
+#undef QG_Y
   GPTQ_CHECK_LAUNCH(who);
   if (part) {
     const size_t MN = (size_t)M * N;
@@ -486,7 +520,7 @@ extern "C" int gptq_quant_gemm(const void* x, int x_dtype, int ldx, int M, const
 
 extern "C" size_t gptq_quant_gemm_perm_workspace_bytes(int M, int K, int N, int bits, int groupsize) {
   (void)groupsize;
-  if (M <= 0 || N <= 0 || K <= 0 || K % 32 || (bits != 3 && bits != 4)) return 0;
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32 || (bits != 2 && bits != 3 && bits != 4 && bits != 8)) return 0;
   return qg_perm_workspace_bytes(qg_plan(M, K, N, bits), M, K, N);
 }
 

@@ -260,8 +260,8 @@ def fasterquant_sharded(solvers, bits: int, group=None, blocksize: int = 128, pe
     tables) plus `qweight`; returns [(qweight, scale_table [R, G], zero_table [R, G])] per solver."""
     from . import gptq as gmod
     from .quant import dequant_packed, pack_codes
-    if bits not in (3, 4):
-        raise NotImplementedError("sharded runs exchange packed weights: bits must be 3 or 4")
+    if bits not in (2, 3, 4, 8):
+        raise NotImplementedError("sharded runs exchange packed weights: bits must be 2, 3, 4 or 8")
     if groupsize > 0 and actorder and not static_groups:
         raise NotImplementedError("sharded runs need static groups with act-order (no g_idx in the packed format)")
     solvers = list(solvers)

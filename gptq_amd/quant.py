@@ -1,9 +1,11 @@
-"""Affine weight quantizer and packed 3/4-bit Linear modules on MI355X.
+"""Affine weight quantizer and packed 2/3/4/8-bit Linear modules on MI355X.
 
 Mirrors the reference's `quant.py` surface (`quantize`, `Quantizer`, `Quant3Linear`,
 `make_quant3`) plus the int4 module whose layout the reference pins in
-zeroShot/models/quant.py:172-209.  All arithmetic on the hot path runs in
-libgptq_hip.so; torch only owns memory.
+zeroShot/models/quant.py:172-209, and 2- and 8-bit modules on the same rule (the other
+widths the drivers' `--wbits` offers): code i of a column in word i // (32/bits) at bit
+bits * (i % (32/bits)).  All arithmetic on the hot path runs in libgptq_hip.so; torch
+only owns memory.
 """
 from __future__ import annotations
 
@@ -101,8 +103,21 @@ class Quantizer(nn.Module):
         return torch.all(self.scale != 0)
 
 
+PACKED_BITS = (2, 3, 4, 8)
+
+
+def _check_bits(bits, who):
+    bits = int(bits)
+    if bits not in PACKED_BITS:
+        raise ValueError(f"{who}: bits must be 2, 3, 4 or 8, got {bits}")
+    return bits
+
+
 def _pack(weight, scales, zeros_scaled, bits):
     """[out, in] weights on the grid -> int32 [in/32*bits, out] (quant.py:158-186 / zeroShot quant.py:176-185)."""
+    bits = _check_bits(bits, "_pack")
+    if weight.dim() != 2 or weight.shape[1] % 32:
+        raise ValueError("_pack: weight must be [out, in] with in a multiple of 32")
     dev = _dev_of(weight)
     w = weight if weight.stride(-1) == 1 else weight.contiguous()
     n_out, n_in = w.shape
@@ -117,6 +132,9 @@ def _pack(weight, scales, zeros_scaled, bits):
 
 def pack_codes(codes, bits):
     """uint8 integer codes [out, in] -> int32 [in/32*bits, out]; same layouts as `_pack`."""
+    bits = _check_bits(bits, "pack_codes")
+    if codes.dim() != 2 or codes.shape[1] % 32 or codes.dtype != torch.uint8:
+        raise ValueError("pack_codes: codes must be uint8 [out, in] with in a multiple of 32")
     dev = _dev_of(codes)
     c = codes.contiguous()
     n_out, n_in = c.shape
@@ -143,6 +161,9 @@ def dequant_packed(qweight, scale, zero, bits, groupsize, dtype=torch.float16, p
     """int32 [in/32*bits, out] + grids [G, out] (`zero` = integer zero point) -> dense [out, in] weights,
     computed as scale * (code - zero) like the solver itself (quant.py:10).  `perm` (int32 [in]): the act-order format,
     storage row j is written back to input column perm[j]."""
+    bits = _check_bits(bits, "dequant_packed")
+    if qweight.dim() != 2 or qweight.dtype != torch.int32 or qweight.shape[0] % bits:
+        raise ValueError(f"dequant_packed: qweight must be int32 [in/32*{bits}, out]")
     n_out = qweight.shape[1]
     n_in = qweight.shape[0] // bits * 32
     if perm is not None:
@@ -166,7 +187,7 @@ def pack_grouped(weight, scales, zeros, groupsize, bits, perm=None):
     """[out, in] weights on grouped grids -> int32 [in/32*bits, out] (gptq_pack_grouped).  scales / zeros: [in/groupsize,
     out] (zeros = zero*scale).  With `perm` (int32 [in]) storage row j holds input column perm[j] on the grid of group
     j // groupsize: the act-order format.  Each code is clamp(round((w + zeros) / scales), 0, 2^bits - 1)."""
-    bits, groupsize = int(bits), int(groupsize)
+    bits, groupsize = _check_bits(bits, "pack_grouped"), int(groupsize)
     w = weight if weight.stride(-1) == 1 else weight.contiguous()
     n_out, n_in = w.shape
     if groupsize <= 0 or groupsize % 32 or n_in % groupsize:
@@ -201,8 +222,7 @@ def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_d
     if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(f"quant_matmul: out_dtype must be fp32, fp16 or bf16, got {out_dtype}")
     bits, groupsize = int(bits), int(groupsize)
-    if bits not in (3, 4):
-        raise ValueError(f"quant_matmul: bits must be 3 or 4, got {bits}")
+    bits = _check_bits(bits, "quant_matmul")
     if qweight.dtype != torch.int32 or qweight.dim() != 2:
         raise ValueError("quant_matmul: qweight must be an int32 [K/32*bits, N] tensor")
     K, N = x.shape[-1], qweight.shape[1]
@@ -347,6 +367,38 @@ class Quant4Linear(_QuantLinearBase):
         quant_cuda.vecquant4matmul(x, self.qweight, y, self.scales, self.zeros)
 
 
+class _QuantPow2Linear(_QuantLinearBase):
+    """Per-row packed Linear of a width that divides 32 (2 / 8 bits): the 4-bit module's rule with 16 / 4 codes per
+    word, qweight int32 [in/32*bits, out].  Same constructor forms and buffers as Quant4Linear."""
+
+    def __init__(self, infeatures, outfeatures=None, zeros=None, faster=False, multi_token=False):
+        super().__init__()
+        self.faster = faster
+        self.multi_token = multi_token
+        if isinstance(infeatures, nn.Module):
+            linear, scales = infeatures, outfeatures
+            self._alloc(linear.in_features, linear.out_features)
+            self.pack(linear, scales, zeros)
+        else:
+            self._alloc(infeatures, outfeatures)
+
+
+class Quant2Linear(_QuantPow2Linear):
+    """2-bit packed Linear: code i of a column in word i // 16 at bit 2 * (i % 16)."""
+    bits = 2
+
+    def _matvec(self, x, y):
+        quant_cuda.vecquant2matmul(x, self.qweight, y, self.scales, self.zeros)
+
+
+class Quant8Linear(_QuantPow2Linear):
+    """8-bit packed Linear: code i of a column in byte i % 4 of word i // 4."""
+    bits = 8
+
+    def _matvec(self, x, y):
+        quant_cuda.vecquant8matmul(x, self.qweight, y, self.scales, self.zeros)
+
+
 class QuantGroupLinear(nn.Module):
     """Packed Linear with one (scale, zero) per `groupsize` input columns.
 
@@ -362,8 +414,8 @@ class QuantGroupLinear(nn.Module):
     def __init__(self, bits, groupsize, infeatures, outfeatures, multi_token=False, act_order=False):
         super().__init__()
         self.multi_token = multi_token
-        if bits not in (3, 4) or groupsize % 32 or infeatures % groupsize:
-            raise ValueError("QuantGroupLinear: bits in {3,4}, groupsize % 32 == 0, in_features % groupsize == 0")
+        if bits not in PACKED_BITS or groupsize <= 0 or groupsize % 32 or infeatures % groupsize:
+            raise ValueError("QuantGroupLinear: bits in {2,3,4,8}, groupsize % 32 == 0, in_features % groupsize == 0")
         self.bits, self.groupsize = bits, groupsize
         self.act_order = bool(act_order)
         self.register_buffer('qweight', torch.zeros((infeatures // 32 * bits, outfeatures), dtype=torch.int))
@@ -456,6 +508,17 @@ def make_quant3(module, names, name='', faster=False, multi_token=False):
 
 def make_quant4(module, names, name='', faster=False, multi_token=False):
     _make_quant(module, names, name, Quant4Linear, faster, multi_token)
+
+
+def make_quant2(module, names, name='', faster=False, multi_token=False):
+    _make_quant(module, names, name, Quant2Linear, faster, multi_token)
+
+
+def make_quant8(module, names, name='', faster=False, multi_token=False):
+    _make_quant(module, names, name, Quant8Linear, faster, multi_token)
+
+
+PACKED_LINEAR = {2: Quant2Linear, 3: Quant3Linear, 4: Quant4Linear, 8: Quant8Linear}   # per-row module of each width
 
 
 def _make_quant(module, names, name, cls, faster, multi_token=False):

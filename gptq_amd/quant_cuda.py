@@ -67,9 +67,24 @@ def vecquant4matmul(vec, mat, mul, scales, zeros):
     _run("gptq_vecquant4matmul", 4, vec, mat, mul, scales, zeros, vec.dtype if vec.dtype == torch.float16 else torch.float32)
 
 
+def vecquant2matmul(vec, mat, mul, scales, zeros):
+    """2-bit analogue (code i of a column in word i // 16 at bit 2 * (i % 16)); vec fp32 or fp16."""
+    _run("gptq_vecquant2matmul", 2, vec, mat, mul, scales, zeros, vec.dtype if vec.dtype == torch.float16 else torch.float32)
+
+
+def vecquant8matmul(vec, mat, mul, scales, zeros):
+    """8-bit analogue (code i of a column in byte i % 4 of word i // 4); vec fp32 or fp16."""
+    _run("gptq_vecquant8matmul", 8, vec, mat, mul, scales, zeros, vec.dtype if vec.dtype == torch.float16 else torch.float32)
+
+
 def vecquant_matmul_grouped(vec, mat, mul, scales, zeros, bits, groupsize, perm=None):
     """Grouped-grid mat-vec: scales / zeros are [in/groupsize, out], zeros = zero*scale.  `perm` (int32
     [in]): the act-order format, packed row k multiplies vec[perm[k]] (gptq_vecquant_matmul_grouped_perm)."""
+    bits, groupsize = int(bits), int(groupsize)
+    if bits not in (2, 3, 4, 8):
+        raise ValueError(f"vecquant_matmul_grouped: bits must be 2, 3, 4 or 8, got {bits}")
+    if groupsize <= 0 or groupsize % 32:
+        raise ValueError("vecquant_matmul_grouped: groupsize must be a positive multiple of 32")
     if perm is not None:
         from .quant import check_perm
         perm = check_perm(perm, mat.shape[0] // bits * 32, vec, "vecquant_matmul_grouped")

@@ -139,8 +139,8 @@ def quantize_sequential(model, dataloader, dev, args: QuantArgs, group=None, tim
     import torch.distributed as dist
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
-    if world > 1 and args.wbits not in (3, 4):
-        raise NotImplementedError("sharded runs exchange packed weights: wbits must be 3 or 4")
+    if world > 1 and args.wbits not in (2, 3, 4, 8):
+        raise NotImplementedError("sharded runs exchange packed weights: wbits must be 2, 3, 4 or 8")
     from . import gptq as _gptq_mod
     old_defer = _gptq_mod.HESSIAN_DEFER
     # deferral is safe here: every hooked forward produces fresh activation tensors and nothing below writes into them
@@ -491,14 +491,16 @@ def _set_module(root, dotted, new):
 def pack_model(model, quantizers, bits, faster=False, multi_token=False):
     """Replace every quantized Linear by a packed module in place, like `opt_pack3` (opt.py:362-373).
 
-    Per-row runs (groupsize = -1) give `Quant3Linear` / `Quant4Linear`.  Grouped runs, whose quantizers carry the group
+    Per-row runs (groupsize = -1) give the per-row module of the width (`Quant2Linear` ... `Quant8Linear`).  Grouped runs, whose quantizers carry the group
     grids (`group_scale`, see quantize_sequential), give `QuantGroupLinear`; act-order with dynamic groups packs in the
     permuted order with a `perm` buffer (`act_order=True`), every other grouped run in original order.  The packing
     itself happens on the GPU (the reference loops over rows in numpy, "TODO: perform packing on GPU", opt.py:361).
     `multi_token=True` lets the packed model run inputs of several tokens (prefill, `eval_ppl`) through the dequant
     GEMM.  (`faster` applies to the 3-bit per-row module only.)"""
-    from .quant import Quant3Linear, Quant4Linear, QuantGroupLinear
-    cls = {3: Quant3Linear, 4: Quant4Linear}[bits]
+    from .quant import PACKED_LINEAR, QuantGroupLinear
+    if bits not in PACKED_LINEAR:
+        raise ValueError(f"pack_model: bits must be 2, 3, 4 or 8, got {bits}")
+    cls = PACKED_LINEAR[bits]
     layers = find_layers(model)
     for name, q in quantizers.items():
         lin = layers[name]
@@ -519,6 +521,9 @@ def make_packed_skeleton(model, names, bits, faster=False, multi_token=False, gr
     `qweight / scales / zeros / bias` (and `perm`).  groupsize > 0 builds `QuantGroupLinear` modules for checkpoints of
     grouped runs; `act_order=True` gives them the `perm` buffer of the act-order format (act-order runs with dynamic
     groups -- act-order runs with static groups use the plain grouped format and load with act_order=False)."""
+    from .quant import PACKED_LINEAR
+    if bits not in PACKED_LINEAR:
+        raise ValueError(f"make_packed_skeleton: bits must be 2, 3, 4 or 8, got {bits}")
     if groupsize > 0:
         from .quant import QuantGroupLinear
         layers = find_layers(model)
@@ -527,8 +532,8 @@ def make_packed_skeleton(model, names, bits, faster=False, multi_token=False, gr
             _set_module(model, name, QuantGroupLinear(bits, groupsize, lin.in_features, lin.out_features,
                                                       multi_token=multi_token, act_order=act_order))
         return model
-    from .quant import make_quant3, make_quant4
-    (make_quant3 if bits == 3 else make_quant4)(model, names, faster=faster, multi_token=multi_token)
+    from .quant import _make_quant
+    _make_quant(model, names, '', PACKED_LINEAR[bits], faster, multi_token)
     return model
 
 

@@ -224,7 +224,8 @@ int gptq_fasterquant_rows_factored(float* W, int ldw, float* H, int ldh, int R, 
  * weight: [out, in] row-major (dtype w_dtype, leading dimension ldw);
  * scales [out] fp32; zeros [out] fp32 = zero*scale (quant.py:153);
  * qweight: int32 [in/32*bits, out] (bits = 3: 96-bit little-endian stream per
- * 32 codes; bits = 4: nibble i%8 of word i/8).  in % 32 == 0 (3-bit) / in % 8 == 0.
+ * 32 codes; bits = 4: nibble i%8 of word i/8; bits = 2 / 8: the same rule with 16 / 4
+ * codes per word, code i in word i/(32/bits) at bit bits*(i%(32/bits))).  in % 32 == 0.
  * gptq_pack_codes packs ready integer codes (uint8 [out, in]) instead.
  * ------------------------------------------------------------------------- */
 int gptq_pack_weights(const void* weight, int w_dtype, int ldw, int out_features, int in_features,
@@ -263,12 +264,19 @@ int gptq_dequant_packed_perm(const int32_t* qweight, const float* scale, const f
  *   mul[col] += sum_k (scales[col]*q[k,col] - zeros[col]) * vec[k]
  * vec: [in] (vec_dtype GPTQ_F32, or GPTQ_F16 for the "faster" form); mat int32
  * [height, width], height = in/32*bits, width = out; mul/scales/zeros fp32 [width].
- * vecquant4matmul has no reference kernel (only the layout is pinned, see above).
+ * vecquant4matmul has no reference kernel (only the layout is pinned, see above);
+ * vecquant2matmul / vecquant8matmul are the same for the 2- and 8-bit layouts.
  * ------------------------------------------------------------------------- */
 int gptq_vecquant3matmul(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
                          const float* scales, const float* zeros, int height, int width,
                          gptq_stream_t stream);
 int gptq_vecquant4matmul(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
+                         const float* scales, const float* zeros, int height, int width,
+                         gptq_stream_t stream);
+int gptq_vecquant2matmul(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
+                         const float* scales, const float* zeros, int height, int width,
+                         gptq_stream_t stream);
+int gptq_vecquant8matmul(const void* vec, int vec_dtype, const int32_t* mat, float* mul,
                          const float* scales, const float* zeros, int height, int width,
                          gptq_stream_t stream);
 
@@ -291,7 +299,7 @@ int gptq_vecquant_matmul_grouped_perm(const void* vec, int vec_dtype, const int3
  * one token):
  *   y[m][n] = sum_k x[m][k] * (scales[g][n]*q[k][n] - zeros[g][n]) (+ bias[n]),   g = k / groupsize
  * x: [M, K] row-major, x_dtype GPTQ_F16 or GPTQ_BF16, leading dimension ldx >= K; qweight int32 [K/32*bits, N] in the
- * layouts above (bits 3 or 4, K % 32 == 0); scales / zeros fp32 (zeros = zero*scale): [N] when groupsize <= 0, else
+ * layouts above (bits 2, 3, 4 or 8, K % 32 == 0); scales / zeros fp32 (zeros = zero*scale): [N] when groupsize <= 0, else
  * [K/groupsize, N] with groupsize % 32 == 0 and K % groupsize == 0; bias fp32 [N] or NULL; y: [M, N], y_dtype GPTQ_F32,
  * GPTQ_F16 or GPTQ_BF16, leading dimension ldy >= N.  fp32 accumulation on the exact integer codes, the grid applied per
  * group as scale*sum(q*x) - zero*sum(x), bias added in fp32, one rounding to y_dtype.  workspace: at least

@@ -7,7 +7,10 @@ fp16 GEMV with vecquant3matmul (fp32 and fp16 activations) and vecquant4matmul, 
 quantized output against the dense one.  Reports microseconds per call and achieved HBM GB/s on the
 ALGORITHMIC bytes (in/32*bits*out*4 + in*sizeof(x) + out*16), MI355X peak 8000 GB/s.
 
-    python tools/bench_kernel.py [--in 36864 --out 9216 --iters 200]
+    python tools/bench_kernel.py [--in 36864 --out 9216 --iters 200 --bits 3 4]
+
+`--bits` picks the packed widths (any of 2, 3, 4, 8; default 3 4).  "packed_TBps" is the rate on the packed bytes alone,
+the figure to compare between widths.
 """
 import argparse
 import json
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--in", dest="n_in", type=int, default=36864)
     ap.add_argument("--out", dest="n_out", type=int, default=9216)
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--bits", type=int, nargs="+", choices=(2, 3, 4, 8), default=[3, 4])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     gen = torch.Generator(device=dev).manual_seed(0)
@@ -49,7 +53,7 @@ def main():
     W16 = (torch.randn(a.n_out, a.n_in, device=dev, generator=gen) * 0.02).half()
     t = timeit(lambda: torch.mv(W16, x16), a.iters)
     res["fp16_gemv"] = {"us": round(t, 2), "GBps": round(W16.numel() * 2 / t / 1e3, 1)}
-    for bits in (3, 4):
+    for bits in a.bits:
         codes = torch.randint(0, 2 ** bits, (a.n_out, a.n_in), device=dev, generator=gen, dtype=torch.uint8)
         scales = torch.rand(a.n_out, 1, device=dev, generator=gen) * 0.01 + 1e-3
         zeros = torch.randint(0, 2 ** bits, (a.n_out, 1), device=dev, generator=gen).float() * scales
@@ -58,8 +62,8 @@ def main():
         res[f"pack{bits}_codes"] = {"us": round(tp, 2), "GBps": round((codes.numel() + qw.numel() * 4) / tp / 1e3, 1)}
         dense = scales * codes.float() - zeros
         ref = dense.double() @ x32.double()
-        fn = quant_cuda.vecquant3matmul if bits == 3 else quant_cuda.vecquant4matmul
-        fn16 = quant_cuda.vecquant3matmul_faster if bits == 3 else quant_cuda.vecquant4matmul
+        fn = getattr(quant_cuda, f"vecquant{bits}matmul")
+        fn16 = quant_cuda.vecquant3matmul_faster if bits == 3 else fn
         for tag, x, f in (("fp32", x32, fn), ("fp16", x16, fn16)):
             y = torch.zeros(a.n_out, device=dev)
             f(x, qw, y, scales, zeros)
@@ -68,6 +72,7 @@ def main():
             nbytes = qw.numel() * 4 + x.numel() * x.element_size() + a.n_out * 16
             res[f"vecquant{bits}matmul_{tag}"] = {"us": round(t, 2), "GBps": round(nbytes / t / 1e3, 1),
                                                    "frac_hbm_peak": round(nbytes / t / 1e3 / PEAK, 3),
+                                                   "packed_TBps": round(qw.numel() * 4 / t / 1e6, 3),
                                                    "bytes": nbytes, "max_rel_err": err}
     print(json.dumps(res))
 

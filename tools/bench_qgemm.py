@@ -1,12 +1,13 @@
 """Packed dequant GEMM (gptq_amd.quant_matmul) against dense fp16 torch.nn.functional.linear on the Llama-7B Linears.
 
-    python tools/bench_qgemm.py [--iters 30] [--json out.json] [--perm]
+    python tools/bench_qgemm.py [--iters 30] [--json out.json] [--perm] [--bits 2 4 8] [--ms 1 16 2048]
 
 Shapes 4096->4096, 4096->11008, 11008->4096; M in {2, 8, 16, 64, 256, 2048}; 3-bit per-row and 4-bit g128 grids.  The
 two are timed alternately in one process with device events after a warm-up, each as a graph of 20 back-to-back
 calls (per-call host launch cost would otherwise set a ~20 us floor on both); reported: median time, TFLOP/s, GB/s of
 the packed weight bytes, and the share of the roof that bounds the case (2.5 PF fp16 MFMA, 8 TB/s HBM; the bytes
-counted are weights + activations + output).
+counted are weights + activations + output).  --bits: these packed widths (any of 2, 3, 4, 8), all on g128 grids, so
+that the widths compare on one grid; --ms: these M instead.
 
 --perm: the act-order format instead (4-bit g128, storage row k = input column perm[k], a random permutation): the
 grouped GEMM with perm (gptq_quant_gemm_perm) against the same GEMM without it on the same packed weights, M in
@@ -141,6 +142,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--json", default=None)
     ap.add_argument("--perm", action="store_true", help="the act-order format: GEMM and mat-vec with / without perm")
+    ap.add_argument("--bits", type=int, nargs="+", choices=(2, 3, 4, 8), default=None,
+                    help="packed widths, each on a g128 grid (default: 3-bit per-row and 4-bit g128)")
+    ap.add_argument("--ms", type=int, nargs="+", default=None, help=f"the M to run (default {MS})")
     args = ap.parse_args()
     from gptq_amd.build import ensure_built
     ensure_built()
@@ -155,7 +159,7 @@ def main():
     rows = []
     for K, N in SHAPES:
         Wd = (torch.randn(N, K, device=dev, generator=gen) * 0.02).half()
-        for bits, gs in GRIDS:
+        for bits, gs in ([(b, 128) for b in args.bits] if args.bits else GRIDS):
             codes = torch.randint(0, 2 ** bits, (N, K), device=dev, generator=gen, dtype=torch.int32).to(torch.uint8)
             qw = pack_codes(codes, bits)
             ng = K // gs if gs > 0 else 1
@@ -164,7 +168,7 @@ def main():
             if gs <= 0:
                 s, z = s[0].contiguous(), z[0].contiguous()
             packed_bytes = qw.numel() * 4 + 2 * s.numel() * 4
-            for M in MS:
+            for M in (args.ms or MS):
                 x = torch.randn(M, K, device=dev, generator=gen).half()
                 # preallocated outputs / workspace and the C entry point: the kernels, not the wrapper, are timed
                 # (gptq_amd.quant_matmul adds its host-side checks and allocations to every call)
