@@ -9,4 +9,6 @@ from .quant import (Quant2Linear, Quant3Linear, Quant4Linear, Quant8Linear, Quan
                     Quantizer, make_quant2, make_quant3, make_quant4, make_quant8, pack_codes, pack_grouped,
                     quant_matmul, quantize, set_multi_token)
 
+from .sequential import QuantArgs, check_wbits, packed_wbits, wbits_for  # noqa: F401
+
 __version__ = "0.1.0"

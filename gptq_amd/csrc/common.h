@@ -57,6 +57,11 @@ int lookahead_mask();               // bit 0: factorization chain, bit 1: column
 // stream's far-update GEMMs that share their SIMDs (s_setprio: 0 = default ... 3).
 #if defined(__HIPCC__)
 __device__ __forceinline__ void critical_path_priority() { __builtin_amdgcn_s_setprio(3); }
+// maxq = 2^bits - 1 of row r of a mixed-width solve (gptq_fasterquant_rows_mixed).  Callers validate 1..8; the clamp only
+// keeps a stray byte from turning into an undefined shift.
+__device__ __forceinline__ float row_maxq(const uint8_t* __restrict__ row_bits, long r) {
+  return (float)((1 << min(max((int)row_bits[r], 1), 8)) - 1);
+}
 #endif
 
 // Tuning knobs that were measured and settled (each is documented where it is used) are compile-time constants in the

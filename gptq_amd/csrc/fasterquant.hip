@@ -141,11 +141,13 @@ __global__ __launch_bounds__(256) void sum_kernel(const float* __restrict__ x, i
 
 // ---------------------------------------------------------------------------------------------
 // Quantizer.find_params (quant.py:37-77; perchannel, weight=True, mse=False): one wave per (row, group).
+// MIXED: row r takes its width from row_bits[r] (gptq_fasterquant_rows_mixed) instead of the launch's maxq.
 // ---------------------------------------------------------------------------------------------
+template <bool MIXED>
 __global__ __launch_bounds__(256) void find_params_kernel(const float* __restrict__ W, int ldw, int R,
                                                           int c0, int c1, int gsize, float maxq, int sym,
                                                           float* __restrict__ scale, float* __restrict__ zero,
-                                                          int tab_ld, int g0) {
+                                                          int tab_ld, int g0, const uint8_t* __restrict__ row_bits) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int j = blockIdx.y;
@@ -164,6 +166,7 @@ __global__ __launch_bounds__(256) void find_params_kernel(const float* __restric
     mx = fmaxf(mx, __shfl_xor(mx, o));
   }
   if (lane != 0) return;
+  if (MIXED) maxq = row_maxq(row_bits, r);
   float xmin = fminf(mn, 0.f), xmax = fmaxf(mx, 0.f);          // quant.py:56-58
   if (sym) {                                                   // quant.py:60-64
     xmax = fmaxf(fabsf(xmin), xmax);
@@ -218,6 +221,7 @@ struct QuantBlockArgs {
   int wide;                    // bit 0: rows of W / Err / w0 allow 16-byte accesses and the block is full: a phase is
                                // retired through an LDS transpose with 32-byte row pieces per lane instead of 4-byte
                                // scatters; bit 1: the same for the codes (no column map, 8-byte aligned rows)
+  const uint8_t* row_bits;     // MIXED kernels only: the width of every row ([R], 1..8) instead of maxq
 };
 
 // One 32-column phase PH of the block (compile-time, so every "is there a later group" test and every
@@ -259,7 +263,7 @@ __device__ unsigned long long qb_stamps[32];
 #endif
 template <int NPH, bool GROUPED, int PH, int ABL = 0>   // ABL: timing-only diagnostic builds (results are wrong)
 __device__ __forceinline__ void quant_phase(const QuantBlockArgs& a, float (&w)[8 * NPH], float* Us, float* Us_next,
-                                            const int* grp, const int* cmap, float sc, float zr, bool active,
+                                            const int* grp, const int* cmap, float sc, float zr, float maxq, bool active,
                                             long rbase, float* wrow, int c, int tid, float& loss) {
   constexpr int B = 32 * NPH;
   constexpr int NREG = 8 * NPH;
@@ -333,7 +337,7 @@ __device__ __forceinline__ void quant_phase(const QuantBlockArgs& a, float (&w)[
       else if (tail && 32 * ph + il >= a.count) { gsc = 1.f; gzr = 0.f; }
       const float* urow = Us + il * 4 * LDCL;
       const float x = cur[cc];
-      const float code = ABL == 2 ? fminf(fmaxf(rintf(x * gsc) + gzr, 0.f), a.maxq) : affine_code(x, gsc, gzr, a.maxq);     // gptq.py:262-264
+      const float code = ABL == 2 ? fminf(fmaxf(rintf(x * gsc) + gzr, 0.f), maxq) : affine_code(x, gsc, gzr, maxq);     // gptq.py:262-264
       const float q = gsc * (code - gzr);
       const float d = urow[cc * LDCL + 8 * ph + t];            // Hinv1[i, i]
       const float err = ABL == 2 ? (x - q) * d : (x - q) / d;  // gptq.py:269
@@ -415,7 +419,8 @@ __device__ __forceinline__ void quant_phase(const QuantBlockArgs& a, float (&w)[
 
 // OCC = 2: at most 256 registers, so that two workgroups fit a compute unit -- for more than 256 workgroups (R > 16384),
 // which otherwise run as two rounds (the kernel's natural allocation is ~290 registers: one wave per SIMD).
-template <int NPH, bool GROUPED, int ABL = 0, int OCC = 1>
+// MIXED: every row clamps its codes at its own maxq (read once, here, into a register).
+template <int NPH, bool GROUPED, int ABL = 0, int OCC = 1, bool MIXED = false>
 __global__ __launch_bounds__(256, OCC) void quant_block_kernel(QuantBlockArgs a) {
   critical_path_priority();
   QB_STAMP(0);
@@ -450,13 +455,14 @@ __global__ __launch_bounds__(256, OCC) void quant_block_kernel(QuantBlockArgs a)
     zr = a.zero_tab[rbase * a.tab_ld];
   }
   float loss = 0.f;
+  const float maxq = MIXED ? row_maxq(a.row_bits, rbase) : a.maxq;
 
   {
     float first[32 * B / 256];
     stage_fetch<NPH, 0, ABL>(a, tid, first);
     stage_store<NPH>(Usb[0], tid, first);
   }
-#define QPHASE(P) if constexpr (NPH > P) quant_phase<NPH, GROUPED, P, ABL>(a, w, Usb[(P) & 1], Usb[((P) + 1) & 1], grp, cmap, sc, zr, active, rbase, wrow, c, tid, loss)
+#define QPHASE(P) if constexpr (NPH > P) quant_phase<NPH, GROUPED, P, ABL>(a, w, Usb[(P) & 1], Usb[((P) + 1) & 1], grp, cmap, sc, zr, maxq, active, rbase, wrow, c, tid, loss)
   QPHASE(0); QPHASE(1); QPHASE(2); QPHASE(3); QPHASE(4); QPHASE(5); QPHASE(6); QPHASE(7);
 #undef QPHASE
   if (active && c == 0) a.loss[row] += 0.5f * loss;               // gptq.py:274
@@ -544,8 +550,8 @@ extern "C" int gptq_find_params(const float* W, int ldw, int R, int c0, int c1, 
   const int ng = cdiv(c1 - c0, gsize);
   GPTQ_CHECK_ARG(tab_ld >= g0 + ng, "gptq_find_params: table too narrow");
   const float maxq = (float)((1 << bits) - 1);
-  find_params_kernel<<<dim3(cdiv(R, 4), ng), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      W, ldw, R, c0, c1, gsize, maxq, sym, scale, zero, tab_ld, g0);
+  find_params_kernel<false><<<dim3(cdiv(R, 4), ng), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      W, ldw, R, c0, c1, gsize, maxq, sym, scale, zero, tab_ld, g0, nullptr);
   GPTQ_CHECK_LAUNCH("find_params_kernel");
   return GPTQ_OK;
 }
@@ -588,15 +594,20 @@ static int launch_quant_block(const QuantBlockArgs& a, int blocksize, bool group
   // any blocksize up to 256 (gptq.py:127 takes any int): the kernel walks 1, 2, 4 or 8 phases of 32 columns (the next
   // power of two: fewer kernel variants to build) and treats the columns past `count` as padding, exactly like the tail
   // block of a matrix
-#define QB_CASE(NPH)                                                                  \
-  case NPH:                                                                           \
-    if (grouped) quant_block_kernel<NPH, true><<<grid, 256, 0, s>>>(a);               \
-    else quant_block_kernel<NPH, false><<<grid, 256, 0, s>>>(a);                      \
-    break;
+#define QB_LAUNCH(NPH, OCC)                                                                               \
+  do {                                                                                                    \
+    if (a.row_bits) {                                                                                     \
+      if (grouped) quant_block_kernel<NPH, true, 0, OCC, true><<<grid, 256, 0, s>>>(a);                   \
+      else quant_block_kernel<NPH, false, 0, OCC, true><<<grid, 256, 0, s>>>(a);                          \
+    } else {                                                                                              \
+      if (grouped) quant_block_kernel<NPH, true, 0, OCC><<<grid, 256, 0, s>>>(a);                         \
+      else quant_block_kernel<NPH, false, 0, OCC><<<grid, 256, 0, s>>>(a);                                \
+    }                                                                                                     \
+  } while (0)
+#define QB_CASE(NPH) case NPH: QB_LAUNCH(NPH, 1); break;
   static const int occ_env = tune_knob("GPTQ_QB_OCC", 0);
   if (blocksize > 64 && blocksize <= 128 && (occ_env == 2 || (occ_env == 0 && grid > 256))) {
-    if (grouped) quant_block_kernel<4, true, 0, 2><<<grid, 256, 0, s>>>(a);
-    else quant_block_kernel<4, false, 0, 2><<<grid, 256, 0, s>>>(a);
+    QB_LAUNCH(4, 2);
     GPTQ_CHECK_LAUNCH("quant_block_kernel");
     return GPTQ_OK;
   }
@@ -609,6 +620,7 @@ static int launch_quant_block(const QuantBlockArgs& a, int blocksize, bool group
       return GPTQ_ERR_UNSUPPORTED;
   }
 #undef QB_CASE
+#undef QB_LAUNCH
   GPTQ_CHECK_LAUNCH("quant_block_kernel");
   return GPTQ_OK;
 }
@@ -625,7 +637,7 @@ extern "C" int gptq_quant_block(float* W, int ldw, int R, int C, int i1, int cou
   GPTQ_CHECK_ARG(ldw >= C && ldu >= C && tab_ld >= 1, "gptq_quant_block: bad leading dimension");
   GPTQ_CHECK_ARG(bits >= 1 && bits <= 8, "gptq_quant_block: bits must be in 1..8");
   QuantBlockArgs a{W, ldw, R, i1, count, U, ldu, scale_tab, zero_tab, tab_ld, col_group,
-                   (float)((1 << bits) - 1), Err, codes, ldc, col_map, loss, blocksize, blocksize, nullptr, 0, 0};
+                   (float)((1 << bits) - 1), Err, codes, ldc, col_map, loss, blocksize, blocksize, nullptr, 0, 0, nullptr};
   a.wide = quant_block_wide(a, blocksize);
   return launch_quant_block(a, blocksize, col_group != nullptr, static_cast<hipStream_t>(stream));
 }
@@ -642,6 +654,7 @@ struct QuantSuperArgs {
   float* loss;
   const float* w0; int ldw0;
   int codes_wide;
+  const uint8_t* row_bits;
 };
 }
 int quant_super_lanes(int R);
@@ -730,7 +743,7 @@ static int fasterquant_rows_impl(float* W, int ldw, float* H, int ldh, int R, in
                                  float* group_scale, float* group_zero, int32_t* perm_out,
                                  uint8_t* codes, float* error_out, float* row_loss, int32_t* info,
                                  void* workspace, size_t workspace_bytes, gptq_stream_t stream,
-                                 const int32_t* dead_in, const int32_t* perm_in);
+                                 const int32_t* dead_in, const int32_t* perm_in, const uint8_t* row_bits);
 
 extern "C" int gptq_fasterquant_rows(float* W, int ldw, float* H, int ldh, int R, int C, int bits, int sym,
                                      int blocksize, float percdamp, int groupsize, int actorder,
@@ -740,7 +753,22 @@ extern "C" int gptq_fasterquant_rows(float* W, int ldw, float* H, int ldh, int R
                                      void* workspace, size_t workspace_bytes, gptq_stream_t stream) {
   return fasterquant_rows_impl(W, ldw, H, ldh, R, C, bits, sym, blocksize, percdamp, groupsize, actorder, static_groups,
                                scale_io, zero_io, preset, group_scale, group_zero, perm_out, codes, error_out, row_loss, info,
-                               workspace, workspace_bytes, stream, nullptr, nullptr);
+                               workspace, workspace_bytes, stream, nullptr, nullptr, nullptr);
+}
+
+// gptq_fasterquant_rows with a width per row: row r is quantized with maxq = 2^row_bits[r] - 1 (its grid and the clamp of
+// its codes); everything else -- the factorization, the column order, the updates -- does not depend on the width, and rows
+// are independent problems given H, so every row comes out bit for bit as in a uniform solve at its width.
+// row_bits == NULL: gptq_fasterquant_rows.
+extern "C" int gptq_fasterquant_rows_mixed(float* W, int ldw, float* H, int ldh, int R, int C, int bits,
+                                           const uint8_t* row_bits, int sym, int blocksize, float percdamp, int groupsize,
+                                           int actorder, int static_groups, float* scale_io, float* zero_io, int preset,
+                                           float* group_scale, float* group_zero, int32_t* perm_out, uint8_t* codes,
+                                           float* error_out, float* row_loss, int32_t* info, void* workspace,
+                                           size_t workspace_bytes, gptq_stream_t stream) {
+  return fasterquant_rows_impl(W, ldw, H, ldh, R, C, bits, sym, blocksize, percdamp, groupsize, actorder, static_groups,
+                               scale_io, zero_io, preset, group_scale, group_zero, perm_out, codes, error_out, row_loss, info,
+                               workspace, workspace_bytes, stream, nullptr, nullptr, row_bits);
 }
 
 // gptq_fasterquant_rows for an H that ALREADY holds what gptq_rfactor_upper leaves (factor form only: see
@@ -756,7 +784,7 @@ extern "C" int gptq_fasterquant_rows_factored(float* W, int ldw, float* H, int l
   GPTQ_CHECK_ARG(use_rform(C, blocksize, groupsize, static_groups), "gptq_fasterquant_rows_factored: factor form only");
   return fasterquant_rows_impl(W, ldw, H, ldh, R, C, bits, sym, blocksize, 0.f, groupsize, actorder, static_groups,
                                scale_io, zero_io, preset, group_scale, group_zero, nullptr, codes, error_out, row_loss, info,
-                               workspace, workspace_bytes, stream, dead_in, perm_in);
+                               workspace, workspace_bytes, stream, dead_in, perm_in, nullptr);
 }
 
 static int fasterquant_rows_impl(float* W, int ldw, float* H, int ldh, int R, int C, int bits, int sym,
@@ -765,7 +793,7 @@ static int fasterquant_rows_impl(float* W, int ldw, float* H, int ldh, int R, in
                                  float* group_scale, float* group_zero, int32_t* perm_out,
                                  uint8_t* codes, float* error_out, float* row_loss, int32_t* info,
                                  void* workspace, size_t workspace_bytes, gptq_stream_t stream,
-                                 const int32_t* dead_in, const int32_t* perm_in) {
+                                 const int32_t* dead_in, const int32_t* perm_in, const uint8_t* row_bits) {
   const bool factored = dead_in != nullptr;
   GPTQ_CHECK_ARG(W && H && scale_io && zero_io && error_out && workspace, "gptq_fasterquant: null pointer");
   GPTQ_CHECK_ARG(R > 0 && C > 0 && ldw >= C && ldh >= C, "gptq_fasterquant: bad sizes");
@@ -809,9 +837,13 @@ static int fasterquant_rows_impl(float* W, int ldw, float* H, int ldh, int R, in
   }
   zero_dead_kernel<<<dim3(cdiv(C, TB), std::min(R, 256)), TB, 0, ps>>>(W, ldw, R, C, ws.dead);   // (usually nothing is dead: few workgroups)
   // static groups: grids of the ORIGINAL, uncompensated columns (gptq.py:157-163)
-  if (use_static)
-    find_params_kernel<<<dim3(cdiv(R, 4), G), 256, 0, ps>>>(W, ldw, R, 0, C, groupsize, maxq, sym,
-                                                            ws.stab, ws.ztab, G, 0);
+  // (a width per row: the MIXED instantiations, picked per launch on the host; the uniform ones are untouched)
+  const bool mixed = row_bits != nullptr;
+  auto find_params = [&](dim3 grid, hipStream_t st, const float* Wf, int ldf, int c0, int c1, int gsize, int g0) {
+    if (mixed) find_params_kernel<true><<<grid, 256, 0, st>>>(Wf, ldf, R, c0, c1, gsize, maxq, sym, ws.stab, ws.ztab, G, g0, row_bits);
+    else find_params_kernel<false><<<grid, 256, 0, st>>>(Wf, ldf, R, c0, c1, gsize, maxq, sym, ws.stab, ws.ztab, G, g0, nullptr);
+  };
+  if (use_static) find_params(dim3(cdiv(R, 4), G), ps, W, ldw, 0, C, groupsize, 0);
   // act-order (gptq.py:165-169)
   float* Wk = W;
   int ldk = ldw;
@@ -830,7 +862,7 @@ static int fasterquant_rows_impl(float* W, int ldw, float* H, int ldh, int R, in
       GPTQ_CHECK_HIP(hipMemcpyAsync(ws.stab, scale_io, sizeof(float) * R, hipMemcpyDeviceToDevice, ps));
       GPTQ_CHECK_HIP(hipMemcpyAsync(ws.ztab, zero_io, sizeof(float) * R, hipMemcpyDeviceToDevice, ps));
     } else {
-      find_params_kernel<<<dim3(cdiv(R, 4), 1), 256, 0, ps>>>(Wk, ldk, R, 0, C, C, maxq, sym, ws.stab, ws.ztab, 1, 0);
+      find_params(dim3(cdiv(R, 4), 1), ps, Wk, ldk, 0, C, C, 0);
     }
   } else {
     col_group_kernel<<<cdiv(C, TB), TB, 0, ps>>>(ws.cgroup, C, use_static ? perm : nullptr, groupsize);
@@ -868,7 +900,7 @@ static int fasterquant_rows_impl(float* W, int ldw, float* H, int ldh, int R, in
     if (qs_lanes) {
       QuantSuperArgs qa{Wk, ldk, R, s0, (s1 - s0) / blocksize, H, ldh, ws.stab, ws.ztab, G, grouped ? ws.cgroup : nullptr, maxq,
                         ErrS, SB, codes, C, perm, ws.loss, ws.W0, C,
-                        (codes && !perm && C % 16 == 0 && al16(codes)) ? 1 : 0};
+                        (codes && !perm && C % 16 == 0 && al16(codes)) ? 1 : 0, row_bits};
       const int rc = launch_quant_super(qa, grouped, qs_lanes, s);
       if (rc != GPTQ_OK) return rc;
     }
@@ -886,12 +918,12 @@ static int fasterquant_rows_impl(float* W, int ldw, float* H, int ldh, int R, in
             GPTQ_CHECK_HIP(hipStreamWaitEvent(s, sc->side_done, 0));
             side_busy = false;
           }
-          find_params_kernel<<<dim3(cdiv(R, 4), ngb), 256, 0, s>>>(Wk, ldk, R, first, c1, groupsize, maxq, sym,
-                                                                   ws.stab, ws.ztab, G, first / groupsize);
+          find_params(dim3(cdiv(R, 4), ngb), s, Wk, ldk, first, c1, groupsize, first / groupsize);
         }
       }
       QuantBlockArgs a{Wk, ldk, R, i1, count, H, ldh, ws.stab, ws.ztab, G,
-                       grouped ? ws.cgroup : nullptr, maxq, Err, codes, C, perm, ws.loss, SB, blocksize, rform ? ws.W0 : nullptr, C, 0};
+                       grouped ? ws.cgroup : nullptr, maxq, Err, codes, C, perm, ws.loss, SB, blocksize, rform ? ws.W0 : nullptr, C, 0,
+                       row_bits};
       a.wide = quant_block_wide(a, blocksize);
       const int rc = launch_quant_block(a, blocksize, grouped, s);
       if (rc != GPTQ_OK) return rc;

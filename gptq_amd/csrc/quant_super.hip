@@ -37,6 +37,7 @@ struct QuantSuperArgs {
   float* loss;
   const float* w0; int ldw0;                         // the original (permuted, dead columns zeroed) weights
   int codes_wide;                                    // codes rows allow 8-byte stores and there is no column map
+  const uint8_t* row_bits;                           // MIXED kernels only: the width of every row ([R], 1..8) instead of maxq
 };
 
 #ifdef GPTQ_DIAG   // diagnostic library only: s_memtime stamps of workgroup 0, block 0 of the LAST launch (tools/qs_phases.py)
@@ -175,7 +176,7 @@ __device__ __forceinline__ void qs_super_step(float (&w)[QS<L>::NT], float (&cd)
 template <int L, bool GROUPED, int PH>
 __device__ __forceinline__ void qs_phase(const QuantSuperArgs& a, int i1_next, bool have_next, float (&w)[QS<L>::NT],
                                          const float (&psc)[QS<L>::NT], const float (&pzr)[QS<L>::NT], float sc, float zr,
-                                         float* Us, float* Ud, float* T0, uint8_t* T1b, const int* cmap, int i1, int c,
+                                         float maxq, float* Us, float* Ud, float* T0, uint8_t* T1b, const int* cmap, int i1, int c,
                                          int row_l, long rbase, bool active, int base4, int swz, int tid, float& loss) {
   constexpr int UBUF = QS<L>::UBUF, UD = QS<L>::UD, SPP = QS<L>::SPP, NBUF = QS<L>::NBUF, NT = QS<L>::NT;
   constexpr int TLD = QS<L>::TLD, CLD = QS<L>::CLD;
@@ -191,7 +192,7 @@ __device__ __forceinline__ void qs_phase(const QuantSuperArgs& a, int i1_next, b
   const bool fetch = PH < 3 || have_next;                      // (workgroup-uniform)
   if (fetch) qs_stage_fetch(a.U, a.ldu, PH < 3 ? i1 : i1_next, (PH + 1) & 3, tid, nxt);
   float cd[NT];                                                // (only this phase's SPP entries are used)
-#define QS_STEP(S) if constexpr (SPP > S) qs_super_step<L, GROUPED, PH, S>(w, cd, psc, pzr, sc, zr, a.maxq, Usb, Udb, c, base4, swz, loss)
+#define QS_STEP(S) if constexpr (SPP > S) qs_super_step<L, GROUPED, PH, S>(w, cd, psc, pzr, sc, zr, maxq, Usb, Udb, c, base4, swz, loss)
   QS_STEP(0); QS_STEP(1); QS_STEP(2); QS_STEP(3);
 #undef QS_STEP
   // This phase's columns are final: into the transpose tiles NOW (the block's retire reads them back row-contiguous).
@@ -339,7 +340,9 @@ __device__ __forceinline__ void qs_retire(const QuantSuperArgs& a, float* T0, co
     }
 }
 
-template <int L, bool GROUPED, int OCC>
+// MIXED (gptq_fasterquant_rows_mixed): every row clamps its codes at its own maxq = 2^row_bits[row] - 1, read ONCE here
+// into a register that lives beside sc / zr; the uniform instantiations keep the launch's maxq in a scalar register.
+template <int L, bool GROUPED, int OCC, bool MIXED = false>
 __global__ __launch_bounds__(256, OCC) void quant_super_kernel(QuantSuperArgs a) {
   critical_path_priority();
   constexpr int ROWS = QS<L>::ROWS, NT = QS<L>::NT, TLD = QS<L>::TLD, UBUF = QS<L>::UBUF, UD = QS<L>::UD, CLD = QS<L>::CLD;
@@ -366,6 +369,7 @@ __global__ __launch_bounds__(256, OCC) void quant_super_kernel(QuantSuperArgs a)
     sc = a.scale_tab[rbase * a.tab_ld];
     zr = a.zero_tab[rbase * a.tab_ld];
   }
+  const float maxq = MIXED ? row_maxq(a.row_bits, rbase) : a.maxq;
   float loss_row = a.loss[rbase];
 
   {                                                            // U rows of block 0, phase 0
@@ -399,13 +403,13 @@ __global__ __launch_bounds__(256, OCC) void quant_super_kernel(QuantSuperArgs a)
     float loss = 0.f;
     const bool have_next = b + 1 < a.nb;
     QS_STAMP(1);
-    qs_phase<L, GROUPED, 0>(a, i1 + 128, have_next, w, psc, pzr, sc, zr, Us, Ud, T0, T1b, cmap, i1, c, row_l, rbase, active, base4, swz, tid, loss);
+    qs_phase<L, GROUPED, 0>(a, i1 + 128, have_next, w, psc, pzr, sc, zr, maxq, Us, Ud, T0, T1b, cmap, i1, c, row_l, rbase, active, base4, swz, tid, loss);
     QS_STAMP(2);
-    qs_phase<L, GROUPED, 1>(a, i1 + 128, have_next, w, psc, pzr, sc, zr, Us, Ud, T0, T1b, cmap, i1, c, row_l, rbase, active, base4, swz, tid, loss);
+    qs_phase<L, GROUPED, 1>(a, i1 + 128, have_next, w, psc, pzr, sc, zr, maxq, Us, Ud, T0, T1b, cmap, i1, c, row_l, rbase, active, base4, swz, tid, loss);
     QS_STAMP(3);
-    qs_phase<L, GROUPED, 2>(a, i1 + 128, have_next, w, psc, pzr, sc, zr, Us, Ud, T0, T1b, cmap, i1, c, row_l, rbase, active, base4, swz, tid, loss);
+    qs_phase<L, GROUPED, 2>(a, i1 + 128, have_next, w, psc, pzr, sc, zr, maxq, Us, Ud, T0, T1b, cmap, i1, c, row_l, rbase, active, base4, swz, tid, loss);
     QS_STAMP(4);
-    qs_phase<L, GROUPED, 3>(a, i1 + 128, have_next, w, psc, pzr, sc, zr, Us, Ud, T0, T1b, cmap, i1, c, row_l, rbase, active, base4, swz, tid, loss);
+    qs_phase<L, GROUPED, 3>(a, i1 + 128, have_next, w, psc, pzr, sc, zr, maxq, Us, Ud, T0, T1b, cmap, i1, c, row_l, rbase, active, base4, swz, tid, loss);
     QS_STAMP(5);
     loss_row += 0.5f * loss;                                   // gptq.py:274
 
@@ -448,16 +452,22 @@ int quant_super_lanes(int R) {
 // Launch for one super-block.  Preconditions (checked by the caller, gptq_fasterquant_rows): factor form, 16-byte
 // aligned rows of W / W0 / Err / U, static or no groups.
 int launch_quant_super(const QuantSuperArgs& a, bool grouped, int lanes, hipStream_t s) {
-#define QS_LAUNCH(LL, GG, OCC)                                                                                     \
+#define QS_LAUNCH(LL, GG, OCC, MM)                                                                                 \
   do {                                                                                                             \
-    GPTQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_super_kernel<LL, GG, OCC>),           \
+    GPTQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_super_kernel<LL, GG, OCC, MM>),       \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)QS<LL>::LDS_BYTES));     \
-    quant_super_kernel<LL, GG, OCC><<<cdiv(a.R, QS<LL>::ROWS), 256, QS<LL>::LDS_BYTES, s>>>(a);                   \
+    quant_super_kernel<LL, GG, OCC, MM><<<cdiv(a.R, QS<LL>::ROWS), 256, QS<LL>::LDS_BYTES, s>>>(a);               \
   } while (0)
-  if (lanes == 16) {
-    if (grouped) QS_LAUNCH(16, true, 2); else QS_LAUNCH(16, false, 2);
+  if (a.row_bits) {                                            // a width per row: the MIXED instantiations
+    if (lanes == 16) {
+      if (grouped) QS_LAUNCH(16, true, 2, true); else QS_LAUNCH(16, false, 2, true);
+    } else {
+      if (grouped) QS_LAUNCH(8, true, 2, true); else QS_LAUNCH(8, false, 2, true);
+    }
+  } else if (lanes == 16) {
+    if (grouped) QS_LAUNCH(16, true, 2, false); else QS_LAUNCH(16, false, 2, false);
   } else {
-    if (grouped) QS_LAUNCH(8, true, 2); else QS_LAUNCH(8, false, 2);
+    if (grouped) QS_LAUNCH(8, true, 2, false); else QS_LAUNCH(8, false, 2, false);
   }
 #undef QS_LAUNCH
   GPTQ_CHECK_LAUNCH("quant_super_kernel");

@@ -340,16 +340,42 @@ def fasterquant_many(solvers, blocksize=128, percdamp=.01, groupsize=-1, actorde
         g._solve_finish(state)
 
 
+def _bits_of(q):
+    """Width of a configured quantizer (maxq = 2^bits - 1)."""
+    return int(getattr(q, "wbits", 0)) or (int(q.maxq) + 1).bit_length() - 1
+
+
+def _check_row_bits(row_bits, R):
+    """Per-row widths as the library takes them: a host uint8 tensor [R] with every value in 1..8 (checked here, on the
+    host, before anything is uploaded: the kernels trust them)."""
+    rb = torch.as_tensor(row_bits)
+    if rb.is_cuda:
+        raise ValueError("row_bits must live on the host (they are validated before the upload)")
+    if rb.dim() != 1 or rb.numel() != R:
+        raise ValueError(f"row_bits must hold one width per row ({R}), got shape {tuple(rb.shape)}")
+    if rb.is_floating_point() or rb.dtype == torch.bool:
+        raise ValueError(f"row_bits must be integers, got {rb.dtype}")
+    rb = rb.to(torch.int64)
+    if int(rb.min()) < 1 or int(rb.max()) > 8:
+        raise ValueError("row_bits: every width must be in 1..8")
+    return rb.to(torch.uint8).contiguous()
+
+
 def _enqueue_rows(dev, W, H, quantizer, preset_grid, blocksize, percdamp, groupsize, actorder, static_groups,
-                  factored=None):
+                  factored=None, row_bits=None):
     """Enqueue one gptq_fasterquant_rows call on the CURRENT stream for the rows of `W` [R, C] (fp32, contiguous) with
     the Hessian `H` (consumed: left holding the factor, see `Hinv_form`); nothing here waits for the GPU.  `preset_grid` = (scale, zero) of a
     ready quantizer (gptq.py:181) or None.  `factored` = dict(dead, perm, info): H already holds the factor form
-    (gptq_amd.parallel.rfactor_sharded) of the Hessian that gptq_solve_prepare fixed.  Returns the buffers of the call."""
+    (gptq_amd.parallel.rfactor_sharded) of the Hessian that gptq_solve_prepare fixed.  `row_bits` (host integers [R], each
+    in 1..8): a width per row instead of the quantizer's (gptq_fasterquant_rows_mixed).  Returns the buffers of the call."""
     q = quantizer
     tick = time.time()
-    bits = int(getattr(q, "wbits", 0)) or (int(q.maxq) + 1).bit_length() - 1
+    bits = _bits_of(q)
     R, C = W.shape
+    if row_bits is not None:
+        if factored is not None:
+            raise NotImplementedError("a width per row is not available for solves on a sharded factorization")
+        row_bits = _check_row_bits(row_bits, R).to(dev, non_blocking=False)
     G = -(-C // groupsize) if groupsize > 0 else 0
     scale = torch.zeros(R, device=dev, dtype=torch.float32)
     zero = torch.zeros(R, device=dev, dtype=torch.float32)
@@ -370,7 +396,13 @@ def _enqueue_rows(dev, W, H, quantizer, preset_grid, blocksize, percdamp, groups
                                                   int(bool(static_groups)))
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
-        if factored is None:
+        if row_bits is not None:
+            _lib.call("gptq_fasterquant_rows_mixed", _lib.ptr(W), W.stride(0), _lib.ptr(H), H.stride(0), R, C, bits,
+                      _lib.ptr(row_bits), int(bool(q.sym)), int(blocksize), float(percdamp), int(groupsize),
+                      int(bool(actorder)), int(bool(static_groups)), _lib.ptr(scale), _lib.ptr(zero),
+                      int(preset_grid is not None), _lib.ptr(gscale), _lib.ptr(gzero), _lib.ptr(perm), _lib.ptr(codes),
+                      _lib.ptr(stat), _lib.ptr(row_loss), _lib.ptr(info), _lib.ptr(ws), nbytes, _lib.stream(dev))
+        elif factored is None:
             _lib.call("gptq_fasterquant_rows", _lib.ptr(W), W.stride(0), _lib.ptr(H), H.stride(0), R, C, bits,
                       int(bool(q.sym)), int(blocksize), float(percdamp), int(groupsize), int(bool(actorder)),
                       int(bool(static_groups)), _lib.ptr(scale), _lib.ptr(zero), int(preset_grid is not None),
@@ -385,7 +417,7 @@ def _enqueue_rows(dev, W, H, quantizer, preset_grid, blocksize, percdamp, groups
             info.copy_(factored["info"])          # a non-positive pivot of the (sharded) factorization
     form = lib.gptq_fasterquant_factor_form(C, int(blocksize), int(groupsize), int(bool(static_groups)))
     return dict(tick=tick, W=W, H=H, scale=scale, zero=zero, gscale=gscale, gzero=gzero, perm=perm, codes=codes,
-                stat=stat, ws=ws, row_loss=row_loss, static_groups=bool(static_groups),
+                stat=stat, ws=ws, row_loss=row_loss, row_bits=row_bits, static_groups=bool(static_groups),
                 factor_form="rfactor" if form else "hinv")
 
 
@@ -419,6 +451,7 @@ def _publish_rows(obj, st, a, b, error):
     obj.group_zero = st["gzero"][a:b] if st["gzero"] is not None else None
     obj.perm = st["perm"]
     obj.static_groups = st["static_groups"]
+    obj.joint_rows = st["W"].shape[0]    # rows of the solve this object was part of (its own `rows` when solved alone)
     Q = st["W"][a:b]
     if _Conv1D and isinstance(obj.layer, _Conv1D):
         Q = Q.t()
@@ -426,7 +459,8 @@ def _publish_rows(obj, st, a, b, error):
 
 
 class _JointSolve:
-    """GPTQ objects sharing one running Hessian, solved as one Linear whose rows are theirs stacked (leader first)."""
+    """GPTQ objects sharing one running Hessian, solved as one Linear whose rows are theirs stacked (leader first).
+    Their widths may differ (a --linearmix table: q/k 4 bits, v 3 bits): the rows then carry their own width."""
 
     def __init__(self, members):
         self.members = members
@@ -441,7 +475,7 @@ class _JointSolve:
             q = m.quantizer
             if not isinstance(m.layer, nn.Linear):
                 return False
-            if int(q.maxq) != int(q0.maxq) or bool(q.sym) != bool(q0.sym) or int(q.maxq) < 0:
+            if bool(q.sym) != bool(q0.sym) or int(q.maxq) < 0 or not 1 <= _bits_of(q) <= 8:
                 return False
             if q.scale.numel() == m.rows and bool(q.ready()):          # a preset grid (gptq.py:181): solve alone
                 return False
@@ -470,7 +504,12 @@ class _JointSolve:
         for m in self.members:
             m._applied = m.nsamples if m.nsamples else m._applied
             m._H = None                  # consumed (gptq.py:141-142)
-        st = _enqueue_rows(self.dev, W, H, L.quantizer, None, blocksize, percdamp, groupsize, actorder, static_groups)
+        widths = [_bits_of(m.quantizer) for m in self.members]
+        row_bits = None
+        if len(set(widths)) > 1:         # (uniform groups: today's entry, untouched)
+            row_bits = torch.cat([torch.full((m.rows,), w, dtype=torch.uint8) for m, w in zip(self.members, widths)])
+        st = _enqueue_rows(self.dev, W, H, L.quantizer, None, blocksize, percdamp, groupsize, actorder, static_groups,
+                           row_bits=row_bits)
         bounds, r0 = [], 0
         for m in self.members:
             bounds.append((r0, r0 + m.rows))
@@ -648,6 +687,49 @@ class GPTQ:
         state = self._solve_enqueue(blocksize, percdamp, groupsize, actorder, static_groups)
         self._solve_finish(state)
 
+    def _weight_rows(self):
+        """A private fp32 copy of the layer's weights as the solver takes them: [rows, columns], contiguous."""
+        W = self.layer.weight.data.clone()
+        if isinstance(self.layer, nn.Conv2d):
+            W = W.flatten(1)
+        if _Conv1D and isinstance(self.layer, _Conv1D):
+            W = W.t()
+        return W.float().contiguous()
+
+    @_locked
+    def sensitivity(self, wbits=(2, 3, 4, 8), blocksize=128, percdamp=.01, groupsize=-1, actorder=False,
+                    static_groups=False, lut_quant=False, non_linear_quant=False, columnwise=False):
+        """{bits: error}: the `error` that `fasterquant` with these options would report at each width of `wbits` (what
+        the reference's sensitivity/*.txt tables hold per layer), from ONE factorization: the weights stacked
+        len(wbits) times, every copy with its own width per row, solved on a copy of H.  Nothing the caller can see
+        changes -- `layer.weight`, `quantizer`, `H`, `nsamples`, who shares a Hessian with whom -- so a later
+        `fasterquant` gives what it would have given without this call."""
+        if lut_quant or non_linear_quant or columnwise:
+            raise NotImplementedError("lut_quant / non_linear_quant / columnwise are fork experiments outside "
+                                      "the MI355X hot-path scope")
+        q = self.quantizer
+        if int(q.maxq) < 0:
+            raise NotImplementedError("trits are outside the MI355X hot-path scope")
+        wbits = [int(b) for b in wbits]
+        if not wbits or any(not 1 <= b <= 8 for b in wbits):
+            raise ValueError(f"sensitivity: wbits must be a non-empty sequence of widths in 1..8, got {wbits}")
+        flush_pending()
+        src = self._leader or self       # (a shared running Hessian stays shared: only a copy is consumed)
+        if src._H is None:
+            raise RuntimeError("sensitivity: H was already consumed or freed")
+        H = src._H.clone()               # upper triangle is all the solver reads
+        W = self._weight_rows()
+        R, n = W.shape[0], len(wbits)
+        preset = None
+        if q.scale.numel() == R and bool(q.ready()):             # gptq.py:181: a ready grid is kept at every width
+            preset = (q.scale.reshape(-1).repeat(n), q.zero.reshape(-1).repeat(n))
+        row_bits = torch.tensor(wbits, dtype=torch.uint8).repeat_interleave(R)
+        st = _enqueue_rows(self.dev, W.repeat(n, 1), H, q, preset, blocksize, percdamp, groupsize, actorder, static_groups,
+                           row_bits=row_bits)
+        _check_solved(st)
+        errors = st["row_loss"].view(n, R).sum(1).cpu()
+        return {b: float(e.item()) for b, e in zip(wbits, errors)}
+
     def _solve_enqueue(self, blocksize, percdamp, groupsize, actorder, static_groups):
         """Enqueue the whole solve on the CURRENT stream; nothing here waits for the GPU."""
         q = self.quantizer
@@ -657,12 +739,7 @@ class GPTQ:
             _launch_flush([self._leader or self])
         self._materialize()              # shared running Hessian: this object's own copy ...
         self._release_followers()        # ... and the copies of those that share this one's
-        W = self.layer.weight.data.clone()
-        if isinstance(self.layer, nn.Conv2d):
-            W = W.flatten(1)
-        if _Conv1D and isinstance(self.layer, _Conv1D):
-            W = W.t()
-        W = W.float().contiguous()
+        W = self._weight_rows()
         self._applied = self.nsamples if self.nsamples else self._applied
         H = self._H                      # upper triangle is all the solver reads
         self._H = None                   # consumed, like `del self.H` (gptq.py:141-142)

@@ -17,8 +17,9 @@ The hot path itself (add_batch / fasterquant) is `gptq_amd.GPTQ`.
 """
 from __future__ import annotations
 
+import numbers
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -35,6 +36,12 @@ LLAMA_GROUPS = [['self_attn.k_proj', 'self_attn.v_proj', 'self_attn.q_proj'], ['
 class QuantArgs:
     """The reference CLI flags that reach the hot path (opt.py:514-657, llama.py:344-456)."""
     wbits: int = 4
+    layer_wbits: Optional[Sequence[int]] = None     # mixed widths, one per decoder block (the reference's --layermix table,
+                                                    # quant_bit/layerwise.json); excludes linear_wbits
+    linear_wbits: Optional[Dict[str, int]] = None   # mixed widths by the LAST component of a Linear's name, e.g. {"q_proj": 4,
+                                                    # "v_proj": 3} (--linearmix, quant_bit/linearwise.json); both None: `wbits`
+    sweep_wbits: Tuple[int, ...] = ()               # when set, every Linear's record gains `errors_by_wbits`: GPTQ.sensitivity
+                                                    # at these widths, taken before the real solve
     sym: bool = False
     percdamp: float = 0.01
     groupsize: int = -1
@@ -58,6 +65,43 @@ class QuantArgs:
                                    # end -- from 2048-row into 16384-row GEMMs (288 GB of HBM hold them).  The hooks then see [B, S, C] inputs: the same
                                    # running mean (gptq.py:38-65 takes any batch), but the GEMM library may pick other kernels for the larger shapes,
                                    # so activations and H can differ from the one-by-one run in their last bits.
+
+
+def _check_width(w, what):
+    if isinstance(w, bool) or not isinstance(w, numbers.Integral) or not 1 <= w <= 8:
+        raise ValueError(f"{what}: a width must be an integer in 1..8, got {w!r}")
+    return int(w)
+
+
+def wbits_for(args: QuantArgs, block_index: int, name: str) -> int:
+    """The width of Linear `name` of decoder block `block_index` under `args`: `layer_wbits[block_index]`,
+    `linear_wbits[last component of name]` (the reference's `name.split(".")[-1]`) or, with neither, `wbits`.
+    Pure; ValueError for both tables at once, a block or Linear without an entry, or a width outside 1..8."""
+    if args.layer_wbits is not None and args.linear_wbits is not None:
+        raise ValueError("QuantArgs: layer_wbits and linear_wbits are mutually exclusive")
+    if args.layer_wbits is not None:
+        if not 0 <= block_index < len(args.layer_wbits):
+            raise ValueError(f"QuantArgs.layer_wbits holds {len(args.layer_wbits)} widths, block {block_index} has none")
+        return _check_width(args.layer_wbits[block_index], f"layer_wbits[{block_index}]")
+    if args.linear_wbits is not None:
+        key = name.split(".")[-1]
+        if key not in args.linear_wbits:
+            raise ValueError(f"QuantArgs.linear_wbits has no entry for {key!r} (Linear {name!r})")
+        return _check_width(args.linear_wbits[key], f"linear_wbits[{key!r}]")
+    return args.wbits
+
+
+def check_wbits(args: QuantArgs, block_linears: Sequence[Iterable[str]]) -> Dict[Tuple[int, str], int]:
+    """Validate the width options of `args` against a model given as the Linear names of every decoder block; returns
+    {(block index, name): width}.  Pure host work: the drivers call it before anything touches the GPU."""
+    if args.layer_wbits is not None and args.linear_wbits is not None:
+        raise ValueError("QuantArgs: layer_wbits and linear_wbits are mutually exclusive")
+    if args.layer_wbits is not None and len(args.layer_wbits) != len(block_linears):
+        raise ValueError(f"QuantArgs.layer_wbits holds {len(args.layer_wbits)} widths, the model has "
+                         f"{len(block_linears)} decoder blocks")
+    for w in args.sweep_wbits:
+        _check_width(w, "sweep_wbits")
+    return {(i, n): wbits_for(args, i, n) for i, names in enumerate(block_linears) for n in names}
 
 
 class _Stop(Exception):
@@ -139,7 +183,11 @@ def quantize_sequential(model, dataloader, dev, args: QuantArgs, group=None, tim
     import torch.distributed as dist
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
-    if world > 1 and args.wbits not in (2, 3, 4, 8):
+    widths = set(check_wbits(args, [list(find_layers(l)) for l in _family(model)["layers"]]).values())
+    if world > 1 and (len(widths) > 1 or args.sweep_wbits):
+        raise NotImplementedError("sharded runs exchange packed rows of ONE width and all-reduce H inside the solve: "
+                                  "mixed widths (layer_wbits / linear_wbits) and sweep_wbits need a single process")
+    if world > 1 and not widths <= {2, 3, 4, 8}:
         raise NotImplementedError("sharded runs exchange packed weights: wbits must be 2, 3, 4 or 8")
     from . import gptq as _gptq_mod
     old_defer = _gptq_mod.HESSIAN_DEFER
@@ -305,7 +353,7 @@ def _quantize_sequential(model, dataloader, dev, args, group, world, rank, timin
             for n in names:
                 solvers[n] = GPTQ(full[n])
                 solvers[n].quantizer = Quantizer()
-                solvers[n].quantizer.configure(args.wbits, perchannel=True, sym=args.sym, mse=False)
+                solvers[n].quantizer.configure(wbits_for(args, i, n), perchannel=True, sym=args.sym, mse=False)
 
             # A hooked pass only exists to feed add_batch (its outputs are overwritten by the pass with quantized weights
             # below, opt.py:216-217): once every Linear of the group has seen the sample, the rest of the block forward
@@ -350,9 +398,14 @@ def _quantize_sequential(model, dataloader, dev, args, group, world, rank, timin
             for h in handles:
                 h.remove()
             mover.prefetch_next(i)
+            sweeps = {}
+            if args.sweep_wbits:                                  # (before the real solve: it consumes H)
+                with timed("sweep"):
+                    for n in names:
+                        sweeps[n] = solvers[n].sensitivity(wbits=tuple(args.sweep_wbits), **kw)
             with timed("solve"):
                 if world > 1:
-                    par.fasterquant_sharded([solvers[n] for n in names], bits=args.wbits, group=group, **kw)
+                    par.fasterquant_sharded([solvers[n] for n in names], bits=wbits_for(args, i, names[0]), group=group, **kw)
                 else:
                     fasterquant_many([solvers[n] for n in names], **kw)
             gmod.FLUSH_EVENTS = None
@@ -361,7 +414,10 @@ def _quantize_sequential(model, dataloader, dev, args, group, world, rank, timin
                 quantizers[key] = solvers[n].quantizer
                 if args.groupsize > 0:
                     _attach_groups(solvers[n], args.groupsize, static_groups)
-                records.append(dict(name=key, error=solvers[n].error))
+                records.append(dict(name=key, error=solvers[n].error, wbits=wbits_for(args, i, n),
+                                    joint_rows=getattr(solvers[n], "joint_rows", solvers[n].rows)))
+                if n in sweeps:
+                    records[-1]["errors_by_wbits"] = sweeps[n]
                 solvers[n].free()
             if args.cache_outputs and len(groups) > 1:          # (a single group: its Linears run once after the solve anyway)
                 for n in names:
@@ -418,15 +474,17 @@ def eval_ppl(model, testenc, dev, args: Optional[QuantArgs] = None) -> float:
     model.config.use_cache = False
     fam = _family(model)
     layers = fam["layers"]
+    if args is not None and args.nearest:
+        check_wbits(args, [list(find_layers(l)) for l in layers])
     batches = [testenc[:, i * model.seqlen:(i + 1) * model.seqlen] for i in range(nsamples)]
     inps, kwargs = _capture_layer0(model, fam, batches, nsamples, dev)
     outs = torch.zeros_like(inps)
     for i in range(len(layers)):
         layer = layers[i].to(dev)
         if args is not None and args.nearest:
-            for lin in find_layers(layer).values():
+            for name, lin in find_layers(layer).items():
                 q = Quantizer()
-                q.configure(args.wbits, perchannel=True, sym=args.sym, mse=False)
+                q.configure(wbits_for(args, i, name), perchannel=True, sym=args.sym, mse=False)
                 W = lin.weight.data
                 q.find_params(W, weight=True)
                 lin.weight.data = quantize(W.float(), q.scale, q.zero, q.maxq).to(W.dtype)
@@ -488,7 +546,7 @@ def _set_module(root, dotted, new):
     setattr(parent, parts[-1], new)
 
 
-def pack_model(model, quantizers, bits, faster=False, multi_token=False):
+def pack_model(model, quantizers, bits=None, faster=False, multi_token=False):
     """Replace every quantized Linear by a packed module in place, like `opt_pack3` (opt.py:362-373).
 
     Per-row runs (groupsize = -1) give the per-row module of the width (`Quant2Linear` ... `Quant8Linear`).  Grouped runs, whose quantizers carry the group
@@ -496,21 +554,25 @@ def pack_model(model, quantizers, bits, faster=False, multi_token=False):
     permuted order with a `perm` buffer (`act_order=True`), every other grouped run in original order.  The packing
     itself happens on the GPU (the reference loops over rows in numpy, "TODO: perform packing on GPU", opt.py:361).
     `multi_token=True` lets the packed model run inputs of several tokens (prefill, `eval_ppl`) through the dequant
-    GEMM.  (`faster` applies to the 3-bit per-row module only.)"""
+    GEMM.  (`faster` applies to the 3-bit per-row module only.)  `bits=None` packs every Linear at its own
+    `quantizer.wbits` (mixed-width runs: `layer_wbits` / `linear_wbits`); an int packs all of them at that width."""
     from .quant import PACKED_LINEAR, QuantGroupLinear
-    if bits not in PACKED_LINEAR:
+    if bits is not None and bits not in PACKED_LINEAR:
         raise ValueError(f"pack_model: bits must be 2, 3, 4 or 8, got {bits}")
-    cls = PACKED_LINEAR[bits]
+    widths = {name: int(q.wbits) if bits is None else bits for name, q in quantizers.items()}
+    for name, w in widths.items():                      # (all of them before the first Linear is replaced)
+        if w not in PACKED_LINEAR:
+            raise ValueError(f"pack_model: {name} was quantized to {w} bits; packed widths are 2, 3, 4 and 8")
     layers = find_layers(model)
     for name, q in quantizers.items():
         lin = layers[name]
         if getattr(q, "group_scale", None) is not None:
             act = q.perm is not None and not q.static_groups
-            packed = QuantGroupLinear(bits, q.groupsize, lin.in_features, lin.out_features, multi_token=multi_token,
+            packed = QuantGroupLinear(widths[name], q.groupsize, lin.in_features, lin.out_features, multi_token=multi_token,
                                       act_order=act)
             packed.pack(lin, q.group_scale, q.group_zero, perm=q.perm if act else None)
         else:
-            packed = cls(lin.in_features, lin.out_features, faster=faster, multi_token=multi_token)
+            packed = PACKED_LINEAR[widths[name]](lin.in_features, lin.out_features, faster=faster, multi_token=multi_token)
             packed.pack(lin, q.scale.float(), q.zero.float())
         _set_module(model, name, packed)
     return model
@@ -520,21 +582,40 @@ def make_packed_skeleton(model, names, bits, faster=False, multi_token=False, gr
     """Empty packed modules for `names` (the load side of opt.py:375-402): load_state_dict then fills
     `qweight / scales / zeros / bias` (and `perm`).  groupsize > 0 builds `QuantGroupLinear` modules for checkpoints of
     grouped runs; `act_order=True` gives them the `perm` buffer of the act-order format (act-order runs with dynamic
-    groups -- act-order runs with static groups use the plain grouped format and load with act_order=False)."""
+    groups -- act-order runs with static groups use the plain grouped format and load with act_order=False).  `bits`: one
+    width for all of them, or a dict name -> width (mixed-width checkpoints: what `packed_wbits` reads off a packed
+    model)."""
     from .quant import PACKED_LINEAR
-    if bits not in PACKED_LINEAR:
-        raise ValueError(f"make_packed_skeleton: bits must be 2, 3, 4 or 8, got {bits}")
+    names = list(names)
+    if isinstance(bits, dict):
+        missing = [n for n in names if n not in bits]
+        if missing:
+            raise ValueError(f"make_packed_skeleton: no width given for {missing[0]}")
+        widths = {n: bits[n] for n in names}
+    else:
+        widths = {n: bits for n in names}
+    for w in ([bits] if not isinstance(bits, dict) else widths.values()):
+        if w not in PACKED_LINEAR:
+            raise ValueError(f"make_packed_skeleton: bits must be 2, 3, 4 or 8, got {w}")
     if groupsize > 0:
         from .quant import QuantGroupLinear
         layers = find_layers(model)
         for name in names:
             lin = layers[name]
-            _set_module(model, name, QuantGroupLinear(bits, groupsize, lin.in_features, lin.out_features,
+            _set_module(model, name, QuantGroupLinear(widths[name], groupsize, lin.in_features, lin.out_features,
                                                       multi_token=multi_token, act_order=act_order))
         return model
     from .quant import _make_quant
-    _make_quant(model, names, '', PACKED_LINEAR[bits], faster, multi_token)
+    for w in sorted(set(widths.values())):
+        _make_quant(model, [n for n in names if widths[n] == w], '', PACKED_LINEAR[w], faster, multi_token)
     return model
+
+
+def packed_wbits(model) -> Dict[str, int]:
+    """{name: bits} of every packed Linear of `model` (per-row and grouped modules alike): with it the skeleton of a
+    mixed-width checkpoint is rebuilt as `make_packed_skeleton(fresh, list(w), bits=w)`."""
+    from .quant import QuantGroupLinear, _QuantLinearBase
+    return {name: int(m.bits) for name, m in model.named_modules() if isinstance(m, (_QuantLinearBase, QuantGroupLinear))}
 
 
 @torch.no_grad()

@@ -204,6 +204,20 @@ int gptq_fasterquant_rows(float* W, int ldw, float* H, int ldh, int R, int C, in
                           float* row_loss, int32_t* info, void* workspace, size_t workspace_bytes,
                           gptq_stream_t stream);
 
+/* gptq_fasterquant_rows with a width per row: row_bits (device uint8 [R], every value in 1..8 -- the caller validates) gives
+ * row r the grid and the code range of maxq = 2^row_bits[r] - 1 (quant.py:73-77 and the clamp of quant.py:9, in
+ * find_params for full rows, static and dynamic groups, and in the column loop).  Nothing else of the solve depends on the
+ * width, so Linears that share H but differ in width (the reference's --linearmix tables: q/k 4 bits, v 3 bits), or one
+ * Linear stacked at several widths (a sensitivity sweep), are ONE solve with one factorization chain, and every row comes
+ * out bit for bit as in a uniform solve at its width.  codes stay uint8; the workspace is that of gptq_fasterquant_rows.
+ * row_bits == NULL: exactly gptq_fasterquant_rows at `bits` (which is otherwise only range-checked). */
+int gptq_fasterquant_rows_mixed(float* W, int ldw, float* H, int ldh, int R, int C, int bits,
+                                const uint8_t* row_bits, int sym, int blocksize, float percdamp, int groupsize,
+                                int actorder, int static_groups, float* scale_io, float* zero_io, int preset,
+                                float* group_scale, float* group_zero, int32_t* perm_out, uint8_t* codes,
+                                float* error_out, float* row_loss, int32_t* info, void* workspace,
+                                size_t workspace_bytes, gptq_stream_t stream);
+
 /* The head of the solve alone: dead-column fix of H's diagonal (gptq.py:143-145; dead_out [C] int32 flags) and, with
  * actorder, perm_out = argsort(diag H, descending) (gptq.py:166).  scratch: [C] floats.  What a factorization spread over
  * several GPUs (gptq_chol_*) needs before it starts. */
