@@ -7,7 +7,7 @@ from .gptq import GPTQ, fasterquant_many, flush_pending  # noqa: F401
 from .modelutils import DEV, find_layers  # noqa: F401
 from .quant import (Quant2Linear, Quant3Linear, Quant4Linear, Quant8Linear, QuantGroupLinear,  # noqa: F401
                     Quantizer, make_quant2, make_quant3, make_quant4, make_quant8, pack_codes, pack_grouped,
-                    quant_matmul, quantize, set_multi_token)
+                    quant_matmul, quant_matmul_t, quantize, set_multi_token)
 
 from .sequential import QuantArgs, check_wbits, packed_wbits, wbits_for  # noqa: F401
 

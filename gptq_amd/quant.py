@@ -214,7 +214,14 @@ def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_d
     qweight int32 [K/32*bits, N] (the modules' layouts); scales / zeros (zeros = zero*scale) hold N values for per-row
     grids (groupsize <= 0) or [K/groupsize, N] for grouped ones; bias [N] or None.  fp32 accumulation, one rounding.
     `perm` (int32 [K], grouped grids only): the act-order format, packed row k multiplies x[..., perm[k]]
-    (gptq_quant_gemm_perm); the result is bit-identical to quant_matmul(x[..., perm], ...) without it."""
+    (gptq_quant_gemm_perm); the result is bit-identical to quant_matmul(x[..., perm], ...) without it.
+
+    Under autograd (`torch.is_grad_enabled() and x.requires_grad`) the same call runs inside `_PackedLinearFn`: the
+    output has the same bits and a `grad_fn` whose backward is `quant_matmul_t`.  The checks below then run inside
+    the Function's forward (still `ValueError`), and an x that is not fp16 / bf16 raises "backward through packed
+    Linears needs fp16/bf16 activations" instead of "x must be fp16 or bf16"."""
+    if _needs_grad(x):
+        return _PackedLinearFn.apply(x, _GemmForward(qweight, scales, zeros, bits, groupsize, bias, out_dtype, perm))
     if x.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"quant_matmul: x must be fp16 or bf16, got {x.dtype}")
     if out_dtype is None:
@@ -278,6 +285,106 @@ def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_d
     return y.reshape(outshape)
 
 
+def quant_matmul_t(grad, qweight, scales, zeros, bits, groupsize=-1, out_dtype=None, perm=None):
+    """grad [..., N] (fp16 / bf16) times the TRANSPOSED packed weights -> [..., K] in `out_dtype` (default grad.dtype),
+    through the transposed dequant GEMM of libgptq_hip.so (gptq_quant_gemm_t): the gradient of `quant_matmul` and of the
+    packed Linears with respect to their input.
+
+    Operands as in `quant_matmul`.  Each weight is formed in fp32 as scale * code - zeros and rounded once to grad's
+    dtype; fp32 accumulation over N, one rounding.  `perm` (int32 [K], grouped grids only): the act-order format,
+    packed row k lands in column perm[k] of the result."""
+    if grad.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"quant_matmul_t: grad must be fp16 or bf16, got {grad.dtype}")
+    if out_dtype is None:
+        out_dtype = grad.dtype
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"quant_matmul_t: out_dtype must be fp32, fp16 or bf16, got {out_dtype}")
+    bits, groupsize = int(bits), int(groupsize)
+    bits = _check_bits(bits, "quant_matmul_t")
+    if qweight.dtype != torch.int32 or qweight.dim() != 2:
+        raise ValueError("quant_matmul_t: qweight must be an int32 [K/32*bits, N] tensor")
+    N = qweight.shape[1]
+    if qweight.shape[0] % bits or qweight.shape[0] == 0:
+        raise ValueError(f"quant_matmul_t: qweight {tuple(qweight.shape)} is no [K/32*{bits}, N] buffer "
+                         "(K must be a multiple of 32)")
+    K = qweight.shape[0] // bits * 32
+    if grad.shape[-1] != N:
+        raise ValueError(f"quant_matmul_t: grad has {grad.shape[-1]} output features, qweight {tuple(qweight.shape)} "
+                         f"implies {N}")
+    if groupsize > 0:
+        if groupsize % 32 or K % groupsize:
+            raise ValueError("quant_matmul_t: groupsize must be a multiple of 32 that divides K")
+        want = (K // groupsize, N)
+        if tuple(scales.shape) != want or tuple(zeros.shape) != want:
+            raise ValueError(f"quant_matmul_t: grouped scales / zeros must be {want}")
+    elif scales.numel() != N or zeros.numel() != N:
+        raise ValueError(f"quant_matmul_t: per-row scales / zeros must hold {N} values")
+    if perm is not None:
+        if groupsize <= 0:
+            raise ValueError("quant_matmul_t: perm (the act-order format) needs grouped grids")
+        perm = check_perm(perm, K, grad, "quant_matmul_t")
+    for name, t in (("grad", grad), ("qweight", qweight), ("scales", scales), ("zeros", zeros)):
+        _lib.require_gpu(t, name)
+    dev = grad.device
+    outshape = list(grad.shape[:-1]) + [K]
+    g2 = grad.reshape(-1, N)
+    if g2.stride(-1) != 1 or (g2.shape[0] > 1 and g2.stride(0) < N):   # (expanded grads, e.g. of sum(), have stride 0)
+        g2 = g2.contiguous()
+    M = g2.shape[0]
+    dx = torch.empty((M, K), dtype=out_dtype, device=dev)
+    if M == 0:
+        return dx.reshape(outshape)
+    qw = qweight.contiguous()
+    s = scales.to(torch.float32).contiguous()
+    z = zeros.to(torch.float32).contiguous()
+    nbytes = _lib.load().gptq_quant_gemm_t_workspace_bytes(M, K, N, bits, groupsize)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _lib.call("gptq_quant_gemm_t", _lib.ptr(g2), _lib.dtype_code(g2), max(g2.stride(0), N), M, _lib.ptr(qw),
+                  _lib.ptr(s), _lib.ptr(z), _lib.ptr(perm), K, N, bits, groupsize, _lib.ptr(dx), _lib.dtype_code(dx),
+                  dx.stride(0), _lib.ptr(ws), nbytes, _lib.stream(dev))
+    return dx.reshape(outshape)
+
+
+def _needs_grad(x):
+    return torch.is_grad_enabled() and x.requires_grad
+
+
+class _GemmForward:
+    """The operands of one packed forward as `_PackedLinearFn` carries them: `forward(x)` is the module's own path
+    (run without grad, so the same bits), the rest is what `quant_matmul_t` needs."""
+
+    def __init__(self, qweight, scales, zeros, bits, groupsize, bias=None, out_dtype=None, perm=None, forward=None):
+        self.qweight, self.scales, self.zeros, self.perm = qweight, scales, zeros, perm
+        self.bits, self.groupsize = int(bits), int(groupsize)
+        self.forward = forward if forward is not None else (
+            lambda x: quant_matmul(x, qweight, scales, zeros, bits, groupsize, bias, out_dtype, perm))
+
+
+class _PackedLinearFn(torch.autograd.Function):
+    """y = packed(x) with a gradient for x only (weights, grids and bias are buffers).  Forward: exactly the path taken
+    without autograd -- the dequant GEMM for several tokens, the mat-vec for one.  Backward: `quant_matmul_t`."""
+
+    @staticmethod
+    def forward(ctx, x, op):
+        if x.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"backward through packed Linears needs fp16/bf16 activations, got {x.dtype}")
+        ctx.op = op
+        ctx.x_dtype = x.dtype
+        with torch.no_grad():
+            return op.forward(x.detach())
+
+    @staticmethod
+    def backward(ctx, grad):
+        op = ctx.op
+        if grad.dtype != ctx.x_dtype:                        # (an fp32 `out_dtype`): the weights round to x's type
+            grad = grad.to(ctx.x_dtype)
+        per_row = op.groupsize <= 0
+        dx = quant_matmul_t(grad, op.qweight, op.scales.reshape(-1) if per_row else op.scales,
+                            op.zeros.reshape(-1) if per_row else op.zeros, op.bits, op.groupsize, ctx.x_dtype, op.perm)
+        return dx, None
+
+
 class _QuantLinearBase(nn.Module):
     bits = 0
 
@@ -307,6 +414,12 @@ class _QuantLinearBase(nn.Module):
         self.qweight = qweight.to(home)
 
     def forward(self, x):
+        if _needs_grad(x):
+            return _PackedLinearFn.apply(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, -1,
+                                                         forward=self._forward))
+        return self._forward(x)
+
+    def _forward(self, x):
         if x.shape[-1] == x.numel():
             outshape = list(x.shape)
             y = self.bias.clone().float()
@@ -485,6 +598,13 @@ class QuantGroupLinear(nn.Module):
         return g
 
     def forward(self, x):
+        if _needs_grad(x):
+            return _PackedLinearFn.apply(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, self.groupsize,
+                                                         perm=self.perm if self.act_order else None,
+                                                         forward=self._forward))
+        return self._forward(x)
+
+    def _forward(self, x):
         perm = self.perm if self.act_order else None
         if x.shape[-1] == x.numel():
             outshape = list(x.shape)

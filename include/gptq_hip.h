@@ -335,6 +335,22 @@ int gptq_quant_gemm_perm(const void* x, int x_dtype, int ldx, int M, const int32
                          gptq_stream_t stream);
 size_t gptq_quant_gemm_perm_workspace_bytes(int M, int K, int N, int bits, int groupsize);
 
+/* Transposed packed dequant GEMM -- the gradient of the packed Linears with respect to their input (weights, grids and
+ * bias are buffers, so this is their whole backward):
+ *   dx[m][c(k)] = sum_n dy[m][n] * W16[k][n],   c(k) = perm ? perm[k] : k,
+ *   W16[k][n]   = round_to_dy_dtype(scales[g][n]*q[k][n] - zeros[g][n]),   g = groupsize > 0 ? k / groupsize : 0.
+ * dy: [M, N] row-major, dy_dtype GPTQ_F16 or GPTQ_BF16, leading dimension lddy >= N; qweight / scales / zeros / bits /
+ * groupsize as in gptq_quant_gemm; perm int32 [K] or NULL (non-NULL needs groupsize > 0: the act-order format, storage
+ * row k belongs to input column perm[k]); dx: [M, K], dx_dtype GPTQ_F32, GPTQ_F16 or GPTQ_BF16, lddx >= K.  W16 is formed
+ * with a separate fp32 multiply and subtract and rounded once to the type of dy; the MFMAs run on dy against W16 (exact
+ * products, fp32 sum over n); one rounding to dx_dtype.  Columns at or past N contribute nothing.  workspace: at least
+ * gptq_quant_gemm_t_workspace_bytes(M, K, N, bits, groupsize) bytes (the query needs no device): where the N range is
+ * split, the partial sums go there and are added in a fixed order.  No atomics: the same call gives bit-identical dx. */
+int gptq_quant_gemm_t(const void* dy, int dy_dtype, int lddy, int M, const int32_t* qweight, const float* scales,
+                      const float* zeros, const int32_t* perm /* nullable */, int K, int N, int bits, int groupsize,
+                      void* dx, int dx_dtype, int lddx, void* workspace, size_t workspace_bytes, gptq_stream_t stream);
+size_t gptq_quant_gemm_t_workspace_bytes(int M, int K, int N, int bits, int groupsize);
+
 #ifdef __cplusplus
 }
 #endif

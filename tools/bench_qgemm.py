@@ -13,7 +13,12 @@ that the widths compare on one grid; --ms: these M instead.
 grouped GEMM with perm (gptq_quant_gemm_perm) against the same GEMM without it on the same packed weights, M in
 {1, 4, 16, 128, 2048}, plus the grouped mat-vec with and without perm on the FC2 shape 36864 -> 9216.  Which gather the
 GEMM used (fused into the X staging, or a pre-pass into the workspace) is read off the workspace query.  With the
-diagnostic library (GPTQ_HIP_LIB=gptq_amd/libgptq_hip_diag.so) GPTQ_QG_PERM_FUSED_M moves the switch between the two."""
+diagnostic library (GPTQ_HIP_LIB=gptq_amd/libgptq_hip_diag.so) GPTQ_QG_PERM_FUSED_M moves the switch between the two.
+
+--backward: the transposed dequant GEMM (gptq_quant_gemm_t, dx = dy . Wdeq^T: the backward of the packed Linears) on the
+same Linears, 4-bit per-row, 4-bit g128 and 4-bit g128 with perm, M in {1, 16, 2048}, beside the route that needs no
+such kernel, in the same process: gptq_dequant_packed(_perm) to a dense fp16 matrix, then torch.matmul(dy, W).  Both
+times and their ratio go to profiles/qgemm_backward.json (or --json)."""
 import argparse
 import json
 import os
@@ -136,8 +141,73 @@ def main_perm(args):
                        "GPTQ_QG_PERM_FUSED_M": os.environ.get("GPTQ_QG_PERM_FUSED_M"), "rows": rows}, f, indent=1)
 
 
+BWD_MS = [1, 16, 2048]
+BWD_GRIDS = [(4, -1, False), (4, 128, False), (4, 128, True)]
+
+
+def main_backward(args):
+    import gptq_amd
+    from gptq_amd import _lib
+    from gptq_amd.quant import dequant_packed, pack_codes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    reps = 20
+    rows = []
+    for K, N in SHAPES:
+        for bits, gs, with_perm in BWD_GRIDS:
+            codes = torch.randint(0, 2 ** bits, (N, K), device=dev, generator=gen, dtype=torch.int32).to(torch.uint8)
+            qw = pack_codes(codes, bits)
+            ng = K // gs if gs > 0 else 1
+            s = (torch.rand(ng, N, device=dev, generator=gen) * 0.01 + 1e-3).contiguous()
+            zint = torch.full_like(s, float(2 ** (bits - 1)))
+            z = (s * zint).contiguous()
+            perm = torch.randperm(K, device=dev, generator=gen).to(torch.int32) if with_perm else None
+            W = torch.empty(N, K, device=dev, dtype=torch.float16)
+            for M in (args.ms or BWD_MS):
+                dy = (torch.randn(M, N, device=dev, generator=gen) * 0.1).half()
+                dx = torch.empty(M, K, device=dev, dtype=torch.float16)
+                dxb = torch.empty(M, K, device=dev, dtype=torch.float16)
+                nb = lib.gptq_quant_gemm_t_workspace_bytes(M, K, N, bits, gs)
+                ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+                kern = lambda: _lib.call("gptq_quant_gemm_t", dy.data_ptr(), _lib.F16, N, M, qw.data_ptr(),  # noqa: E731
+                                         s.data_ptr(), z.data_ptr(), _lib.ptr(perm), K, N, bits, gs, dx.data_ptr(), _lib.F16,
+                                         K, ws.data_ptr(), nb, _lib.stream(dev))
+
+                def base():
+                    if perm is None:
+                        _lib.call("gptq_dequant_packed", qw.data_ptr(), s.data_ptr(), zint.data_ptr(), N, K, bits, gs,
+                                  W.data_ptr(), _lib.F16, K, _lib.stream(dev))
+                    else:
+                        _lib.call("gptq_dequant_packed_perm", qw.data_ptr(), s.data_ptr(), zint.data_ptr(), perm.data_ptr(),
+                                  N, K, bits, gs, W.data_ptr(), _lib.F16, K, _lib.stream(dev))
+                    torch.matmul(dy, W, out=dxb)
+
+                kern()
+                base()
+                torch.cuda.synchronize()
+                assert torch.equal(dx, gptq_amd.quant_matmul_t(dy, qw, s if gs > 0 else s[0], z if gs > 0 else z[0], bits, gs,
+                                                               perm=perm))
+                assert torch.equal(W, dequant_packed(qw, s, zint, bits, gs, torch.float16, perm=perm))
+                diff = float((dx.float() - dxb.float()).abs().max()) / max(float(dxb.float().abs().max()), 1e-30)
+                assert diff < 2e-2, diff                                             # the same product, two routes
+                t_k, t_b = alternate(kern, base, reps, args.warmup, args.iters)
+                r = dict(K=K, N=N, M=M, bits=bits, groupsize=gs, perm=with_perm, qgemm_t_us=t_k * 1e6,
+                         dequant_matmul_us=t_b * 1e6, ratio=t_k / t_b, split=nb > 0, max_rel_diff=diff)
+                rows.append(r)
+                print(f"{K:>5}->{N:<5} {bits}b g{gs:<4}{' perm' if with_perm else '     '} M={M:<5} qgemm_t {r['qgemm_t_us']:9.1f} us"
+                      f"  dequant+matmul {r['dequant_matmul_us']:9.1f} us  ratio {r['ratio']:5.2f}", flush=True)
+    out = args.json or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                    "qgemm_backward.json")
+    with open(out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(dev), "reps_per_graph": reps, "iters": args.iters,
+                   "warmup": args.warmup, "rows": rows}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--backward", action="store_true",
+                    help="the transposed dequant GEMM against dequant_packed + torch.matmul")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--json", default=None)
@@ -150,6 +220,8 @@ def main():
     ensure_built()
     if args.perm:
         return main_perm(args)
+    if args.backward:
+        return main_backward(args)
     import gptq_amd
     from gptq_amd import _lib
     from gptq_amd.quant import pack_codes
