@@ -65,6 +65,9 @@ _SIGNATURES = {
     "gptq_quant_gemm_perm_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "gptq_quant_gemm_t": (C.c_int, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _z, _p]),
     "gptq_quant_gemm_t_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "gptq_quant_gemm_grid_grad": (C.c_int, [_p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "gptq_quant_gemm_grid_grad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "gptq_quant_gemm_grid_grad_perm_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -219,9 +219,10 @@ def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_d
     Under autograd (`torch.is_grad_enabled() and x.requires_grad`) the same call runs inside `_PackedLinearFn`: the
     output has the same bits and a `grad_fn` whose backward is `quant_matmul_t`.  The checks below then run inside
     the Function's forward (still `ValueError`), and an x that is not fp16 / bf16 raises "backward through packed
-    Linears needs fp16/bf16 activations" instead of "x must be fp16 or bf16"."""
-    if _needs_grad(x):
-        return _PackedLinearFn.apply(x, _GemmForward(qweight, scales, zeros, bits, groupsize, bias, out_dtype, perm))
+    Linears needs fp16/bf16 activations" instead of "x must be fp16 or bf16".  Where `scales`, `zeros` or `bias`
+    require grad the call runs inside `_PackedGridFn` (same forward bits), whose backward adds `quant_grid_grad`."""
+    if torch.is_grad_enabled() and (x.requires_grad or _grids_need_grad(scales, zeros, bias)):
+        return _apply_packed(x, _GemmForward(qweight, scales, zeros, bits, groupsize, bias, out_dtype, perm))
     if x.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"quant_matmul: x must be fp16 or bf16, got {x.dtype}")
     if out_dtype is None:
@@ -346,8 +347,78 @@ def quant_matmul_t(grad, qweight, scales, zeros, bits, groupsize=-1, out_dtype=N
     return dx.reshape(outshape)
 
 
-def _needs_grad(x):
-    return torch.is_grad_enabled() and x.requires_grad
+def quant_grid_grad(x, grad, qweight, bits, groupsize=-1, perm=None, bias=True):
+    """The gradients of `quant_matmul` with respect to its grids, with the integer codes frozen
+    (gptq_quant_gemm_grid_grad): x [..., K] and grad [..., N] (the same fp16 / bf16 type, the same leading dimensions)
+    -> (dscales, dzeros, dbias), fp32.  With A = x[..., c(k)]^T grad (never stored; c(k) = perm[k] or k),
+
+        dscales[g][n] = sum_{k in g} q[k][n] A[k][n],   dzeros[g][n] = -sum_{k in g} A[k][n],   dbias[n] = sum_m grad[m][n]
+
+    i.e. the gradients with respect to the STORED tensors (`zeros` = zero*scale).  dscales / dzeros are [K/groupsize, N]
+    for grouped grids and [N] for per-row ones; dbias is [N], or None with `bias=False`.  fp32 accumulation, nothing is
+    rounded to 16 bits, no atomics (the same call gives the same bits)."""
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"quant_grid_grad: x must be fp16 or bf16, got {x.dtype}")
+    if grad.dtype != x.dtype:
+        raise ValueError(f"quant_grid_grad: grad must have x's dtype {x.dtype}, got {grad.dtype}")
+    bits, groupsize = int(bits), int(groupsize)
+    bits = _check_bits(bits, "quant_grid_grad")
+    if qweight.dtype != torch.int32 or qweight.dim() != 2:
+        raise ValueError("quant_grid_grad: qweight must be an int32 [K/32*bits, N] tensor")
+    K, N = x.shape[-1], qweight.shape[1]
+    if K == 0 or K % 32 or qweight.shape[0] != K // 32 * bits:
+        raise ValueError(f"quant_grid_grad: x has {K} input features, qweight {tuple(qweight.shape)} implies "
+                         f"{qweight.shape[0] // bits * 32} (and K must be a multiple of 32)")
+    if grad.shape[-1] != N:
+        raise ValueError(f"quant_grid_grad: grad has {grad.shape[-1]} output features, qweight {tuple(qweight.shape)} "
+                         f"implies {N}")
+    if x.numel() // K != grad.numel() // N:
+        raise ValueError(f"quant_grid_grad: x {tuple(x.shape)} and grad {tuple(grad.shape)} hold different numbers of tokens")
+    if groupsize > 0 and (groupsize % 32 or K % groupsize):
+        raise ValueError("quant_grid_grad: groupsize must be a multiple of 32 that divides K")
+    if perm is not None:
+        if groupsize <= 0:
+            raise ValueError("quant_grid_grad: perm (the act-order format) needs grouped grids")
+        perm = check_perm(perm, K, x, "quant_grid_grad")
+    for name, t in (("x", x), ("grad", grad), ("qweight", qweight)):
+        _lib.require_gpu(t, name)
+    dev = x.device
+    x2, g2 = x.reshape(-1, K), grad.reshape(-1, N)
+    M = x2.shape[0]
+    if x2.stride(-1) != 1 or (M > 1 and x2.stride(0) < K):
+        x2 = x2.contiguous()
+    if g2.stride(-1) != 1 or (M > 1 and g2.stride(0) < N):   # (expanded grads, e.g. of sum(), have stride 0)
+        g2 = g2.contiguous()
+    G = K // groupsize if groupsize > 0 else 1
+    shape = (G, N) if groupsize > 0 else (N,)
+    if M == 0:
+        return (torch.zeros(shape, device=dev), torch.zeros(shape, device=dev),
+                torch.zeros(N, device=dev) if bias else None)
+    ds = torch.empty(shape, dtype=torch.float32, device=dev)
+    dz = torch.empty(shape, dtype=torch.float32, device=dev)
+    db = torch.empty(N, dtype=torch.float32, device=dev) if bias else None
+    qw = qweight.contiguous()
+    lib = _lib.load()
+    query = lib.gptq_quant_gemm_grid_grad_workspace_bytes if perm is None else lib.gptq_quant_gemm_grid_grad_perm_workspace_bytes
+    nbytes = query(M, K, N, bits, groupsize)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _lib.call("gptq_quant_gemm_grid_grad", _lib.ptr(x2), _lib.dtype_code(x2), max(x2.stride(0), K), _lib.ptr(g2),
+                  max(g2.stride(0), N), M, _lib.ptr(qw), _lib.ptr(perm), K, N, bits, groupsize, _lib.ptr(ds), _lib.ptr(dz),
+                  _lib.ptr(db), _lib.ptr(ws), nbytes, _lib.stream(dev))
+    return ds, dz, db
+
+
+def _grids_need_grad(scales, zeros, bias):
+    return scales.requires_grad or zeros.requires_grad or (bias is not None and bias.requires_grad)
+
+
+def _apply_packed(x, op):
+    """The autograd route of one packed forward: `_PackedGridFn` where a grid tensor requires grad, the x-only
+    `_PackedLinearFn` otherwise."""
+    if _grids_need_grad(op.scales, op.zeros, op.bias):
+        return _PackedGridFn.apply(x, op.scales, op.zeros, op.bias, op)
+    return _PackedLinearFn.apply(x, op)
 
 
 class _GemmForward:
@@ -355,14 +426,14 @@ class _GemmForward:
     (run without grad, so the same bits), the rest is what `quant_matmul_t` needs."""
 
     def __init__(self, qweight, scales, zeros, bits, groupsize, bias=None, out_dtype=None, perm=None, forward=None):
-        self.qweight, self.scales, self.zeros, self.perm = qweight, scales, zeros, perm
+        self.qweight, self.scales, self.zeros, self.perm, self.bias = qweight, scales, zeros, perm, bias
         self.bits, self.groupsize = int(bits), int(groupsize)
         self.forward = forward if forward is not None else (
             lambda x: quant_matmul(x, qweight, scales, zeros, bits, groupsize, bias, out_dtype, perm))
 
 
 class _PackedLinearFn(torch.autograd.Function):
-    """y = packed(x) with a gradient for x only (weights, grids and bias are buffers).  Forward: exactly the path taken
+    """y = packed(x) with a gradient for x only (no grid tensor requires grad; see `_PackedGridFn`).  Forward: exactly the path taken
     without autograd -- the dequant GEMM for several tokens, the mat-vec for one.  Backward: `quant_matmul_t`."""
 
     @staticmethod
@@ -383,6 +454,82 @@ class _PackedLinearFn(torch.autograd.Function):
         dx = quant_matmul_t(grad, op.qweight, op.scales.reshape(-1) if per_row else op.scales,
                             op.zeros.reshape(-1) if per_row else op.zeros, op.bits, op.groupsize, ctx.x_dtype, op.perm)
         return dx, None
+
+
+class _PackedGridFn(torch.autograd.Function):
+    """y = packed(x) with gradients for x and for the grids (`scales`, `zeros`, `bias` as tensor inputs; the codes stay
+    frozen).  Forward: exactly the path taken without autograd.  Backward: `quant_matmul_t` for x where it needs one,
+    `quant_grid_grad` for the grids, reshaped to the tensors' own shapes ([out, 1] in the per-row modules).  x is saved
+    only where a grid tensor requires grad."""
+
+    @staticmethod
+    def forward(ctx, x, scales, zeros, bias, op):
+        if x.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"backward through packed Linears needs fp16/bf16 activations, got {x.dtype}")
+        ctx.op = op
+        ctx.x_dtype = x.dtype
+        if any(ctx.needs_input_grad[1:4]):
+            ctx.save_for_backward(x)
+        with torch.no_grad():
+            return op.forward(x.detach())
+
+    @staticmethod
+    def backward(ctx, grad):
+        op = ctx.op
+        if grad.dtype != ctx.x_dtype:
+            grad = grad.to(ctx.x_dtype)
+        per_row = op.groupsize <= 0
+        dx = ds = dz = db = None
+        if ctx.needs_input_grad[0]:
+            dx = quant_matmul_t(grad, op.qweight, op.scales.detach().reshape(-1) if per_row else op.scales.detach(),
+                                op.zeros.detach().reshape(-1) if per_row else op.zeros.detach(), op.bits, op.groupsize,
+                                ctx.x_dtype, op.perm)
+        if any(ctx.needs_input_grad[1:4]):
+            x, = ctx.saved_tensors
+            gs, gz, gb = quant_grid_grad(x, grad, op.qweight, op.bits, op.groupsize, op.perm,
+                                         bias=bool(ctx.needs_input_grad[3]))
+            if ctx.needs_input_grad[1]:
+                ds = gs.reshape(op.scales.shape).to(op.scales.dtype)
+            if ctx.needs_input_grad[2]:
+                dz = gz.reshape(op.zeros.shape).to(op.zeros.dtype)
+            if ctx.needs_input_grad[3]:
+                db = gb.reshape(op.bias.shape).to(op.bias.dtype)
+        return dx, ds, dz, db, None
+
+
+GRID_NAMES = ("scales", "zeros", "bias")
+
+
+def _packed_modules(model):
+    return [m for m in model.modules() if isinstance(m, (_QuantLinearBase, QuantGroupLinear))]
+
+
+def trainable_grids(model, scales=True, zeros=True, bias=True):
+    """Opt in to training the grids of every packed Linear in `model`: the chosen buffers (`scales`, `zeros` = zero*scale,
+    `bias`) become fp32 `nn.Parameter`s under the same names, so `state_dict` keys do not change and checkpoints load
+    both ways; `qweight` (and `perm`) stay buffers, the integer codes stay frozen.  Call it after the modules are packed
+    or loaded.  Returns the new parameters (hand them to an optimizer); `frozen_grids` turns them back into buffers."""
+    params = []
+    for m in _packed_modules(model):
+        for name, on in zip(GRID_NAMES, (scales, zeros, bias)):
+            if on and name in m._buffers:
+                p = nn.Parameter(m._buffers.pop(name).detach().float(), requires_grad=True)
+                m.register_parameter(name, p)
+                params.append(p)
+    return params
+
+
+def frozen_grids(model):
+    """Undo `trainable_grids`: every grid parameter of a packed Linear becomes a buffer again, holding its current
+    (trained) values.  Returns the number of tensors turned back."""
+    n = 0
+    for m in _packed_modules(model):
+        for name in GRID_NAMES:
+            if name in m._parameters:
+                p = m._parameters.pop(name)
+                m.register_buffer(name, p.detach())
+                n += 1
+    return n
 
 
 class _QuantLinearBase(nn.Module):
@@ -414,9 +561,9 @@ class _QuantLinearBase(nn.Module):
         self.qweight = qweight.to(home)
 
     def forward(self, x):
-        if _needs_grad(x):
-            return _PackedLinearFn.apply(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, -1,
-                                                         forward=self._forward))
+        if torch.is_grad_enabled() and (x.requires_grad or _grids_need_grad(self.scales, self.zeros, self.bias)):
+            return _apply_packed(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, -1, self.bias,
+                                                 forward=self._forward))
         return self._forward(x)
 
     def _forward(self, x):
@@ -598,10 +745,10 @@ class QuantGroupLinear(nn.Module):
         return g
 
     def forward(self, x):
-        if _needs_grad(x):
-            return _PackedLinearFn.apply(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, self.groupsize,
-                                                         perm=self.perm if self.act_order else None,
-                                                         forward=self._forward))
+        if torch.is_grad_enabled() and (x.requires_grad or _grids_need_grad(self.scales, self.zeros, self.bias)):
+            return _apply_packed(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, self.groupsize,
+                                                 self.bias, perm=self.perm if self.act_order else None,
+                                                 forward=self._forward))
         return self._forward(x)
 
     def _forward(self, x):

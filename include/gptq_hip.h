@@ -351,6 +351,32 @@ int gptq_quant_gemm_t(const void* dy, int dy_dtype, int lddy, int M, const int32
                       void* dx, int dx_dtype, int lddx, void* workspace, size_t workspace_bytes, gptq_stream_t stream);
 size_t gptq_quant_gemm_t_workspace_bytes(int M, int K, int N, int bits, int groupsize);
 
+/* Grid gradients of the packed Linears -- the gradients of gptq_quant_gemm / gptq_quant_gemm_perm
+ *   y[m][n] = sum_k x[m][c(k)] * (scales[g][n]*q[k][n] - zeros[g][n]) + bias[n],   c(k) = perm ? perm[k] : k,
+ * with respect to the stored scales, zeros (= zero*scale) and bias; the integer codes stay frozen:
+ *   A[k][n]       = sum_m x[m][c(k)] * dy[m][n]                 (never stored),
+ *   dscales[g][n] =  sum_{k in g} q[k][n] * A[k][n],
+ *   dzeros[g][n]  = -sum_{k in g} A[k][n],
+ *   dbias[n]      =  sum_m dy[m][n],                            g = groupsize > 0 ? k / groupsize : 0.
+ * x: [M, K] and dy: [M, N], row-major, both of x_dtype (GPTQ_F16 or GPTQ_BF16), ldx >= K, lddy >= N; qweight / bits /
+ * groupsize as in gptq_quant_gemm; perm int32 [K] or NULL (non-NULL needs groupsize > 0: storage row k pairs with
+ * x[:, perm[k]]).  dscales / dzeros: fp32 [G, N] contiguous, G = K / groupsize (1 for per-row grids); dbias: fp32 [N] or
+ * NULL.  The outputs are overwritten, not accumulated.
+ * Arithmetic contract: the MFMAs (v_mfma_f32_16x16x32_{f16,bf16}) run on x against dy, so every product is exact and the
+ * sum over m is an fp32 chain; q*A is one fp32 multiply by the exact code; the sums over the k of a group are fp32 adds in
+ * a fixed order; nothing is rounded to 16 bits.  Rows of x and dy at or past M and columns at or past N contribute
+ * nothing.  No atomics: the same call gives bit-identical outputs.
+ * workspace: at least gptq_quant_gemm_grid_grad_workspace_bytes(M, K, N, bits, groupsize) bytes without perm and
+ * gptq_quant_gemm_grid_grad_perm_workspace_bytes(...) with it (x[:, perm] is gathered there), 16-byte aligned; the queries
+ * need no device.  Where a group spans several K tiles (per-row grids, large groups) or the tokens are split (small K x N),
+ * partial sums go to the workspace and a second kernel adds them in a fixed order; 0 bytes means one pass. */
+int gptq_quant_gemm_grid_grad(const void* x, int x_dtype, int ldx, const void* dy, int lddy, int M,
+                              const int32_t* qweight, const int32_t* perm /* nullable */, int K, int N, int bits,
+                              int groupsize, float* dscales, float* dzeros, float* dbias /* nullable */,
+                              void* workspace, size_t workspace_bytes, gptq_stream_t stream);
+size_t gptq_quant_gemm_grid_grad_workspace_bytes(int M, int K, int N, int bits, int groupsize);
+size_t gptq_quant_gemm_grid_grad_perm_workspace_bytes(int M, int K, int N, int bits, int groupsize);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,15 @@ diagnostic library (GPTQ_HIP_LIB=gptq_amd/libgptq_hip_diag.so) GPTQ_QG_PERM_FUSE
 --backward: the transposed dequant GEMM (gptq_quant_gemm_t, dx = dy . Wdeq^T: the backward of the packed Linears) on the
 same Linears, 4-bit per-row, 4-bit g128 and 4-bit g128 with perm, M in {1, 16, 2048}, beside the route that needs no
 such kernel, in the same process: gptq_dequant_packed(_perm) to a dense fp16 matrix, then torch.matmul(dy, W).  Both
-times and their ratio go to profiles/qgemm_backward.json (or --json)."""
+times and their ratio go to profiles/qgemm_backward.json (or --json).
+
+--grid-grad: the grid gradients (gptq_quant_gemm_grid_grad: dscales, dzeros, dbias from x and dy, the codes frozen) on the
+same Linears at M = 2048 and M = 16, 4-bit per-row, 4-bit g128, 4-bit g128 with perm and 2-bit g128, beside the dense route
+it replaces, in the same process: A = x.t() @ dy in fp32 (a [K, N] tensor), A times the unpacked codes, both summed per
+group, and dy summed over the tokens (the codes are unpacked once, outside the timed region).  Reported: both times,
+their ratio, the TFLOP/s of 2 M K N over the call and its share of the roof that bounds it, and the peak device memory
+each route adds on top of its operands (torch.cuda.max_memory_allocated around one eager call).  Results go to
+profiles/qgemm_grid_grad.json (or --json)."""
 import argparse
 import json
 import os
@@ -204,8 +212,96 @@ def main_backward(args):
                    "warmup": args.warmup, "rows": rows}, f, indent=1)
 
 
+GRID_MS = [2048, 16]
+GRID_GRIDS = [(4, -1, False), (4, 128, False), (4, 128, True), (2, 128, False)]
+
+
+def peak_extra(fn, dev):
+    """Peak device bytes that one eager call of fn allocates on top of what is live before it."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated(dev) - base
+    del out
+    return peak
+
+
+def main_grid_grad(args):
+    import gptq_amd
+    from gptq_amd import _lib
+    from gptq_amd.quant import pack_codes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    rows = []
+    for K, N in SHAPES:
+        for bits, gs, with_perm in GRID_GRIDS:
+            codes = torch.randint(0, 2 ** bits, (N, K), device=dev, generator=gen, dtype=torch.int32).to(torch.uint8)
+            qw = pack_codes(codes, bits)
+            codes_kn = codes.t().contiguous()                                         # [K, N] in storage order, for the dense route
+            del codes
+            G = K // gs if gs > 0 else 1
+            rows_g = gs if gs > 0 else K
+            perm = torch.randperm(K, device=dev, generator=gen).to(torch.int32) if with_perm else None
+            plong = perm.long() if with_perm else None
+            packed_bytes = qw.numel() * 4
+            for M in (args.ms or GRID_MS):
+                x = torch.randn(M, K, device=dev, generator=gen).half()
+                dy = (torch.randn(M, N, device=dev, generator=gen) * 0.1).half()
+                ds = torch.empty(G, N, device=dev)
+                dz = torch.empty(G, N, device=dev)
+                db = torch.empty(N, device=dev)
+                query = lib.gptq_quant_gemm_grid_grad_perm_workspace_bytes if with_perm else lib.gptq_quant_gemm_grid_grad_workspace_bytes
+                nb = query(M, K, N, bits, gs)
+                ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+                kern = lambda: _lib.call("gptq_quant_gemm_grid_grad", x.data_ptr(), _lib.F16, K, dy.data_ptr(), N, M,  # noqa: E731
+                                         qw.data_ptr(), _lib.ptr(perm), K, N, bits, gs, ds.data_ptr(), dz.data_ptr(),
+                                         db.data_ptr(), ws.data_ptr(), nb, _lib.stream(dev))
+
+                def dense():
+                    xs = x[:, plong] if with_perm else x
+                    A = torch.matmul(xs.float().t(), dy.float())                      # [K, N] fp32
+                    return ((A * codes_kn).view(G, rows_g, N).sum(1), -A.view(G, rows_g, N).sum(1), dy.float().sum(0))
+
+                kern()
+                want = dense()
+                torch.cuda.synchronize()
+                got = gptq_amd.quant_grid_grad(x, dy, qw, bits, gs, perm=perm)
+                diff = 0.0
+                for a, b, w in zip((ds, dz, db), got, want):
+                    assert torch.equal(a.reshape(-1), b.reshape(-1))                  # the wrapper runs the timed call
+                    diff = max(diff, float((a.reshape(-1) - w.reshape(-1)).abs().max()) / max(float(w.abs().max()), 1e-30))
+                assert diff < 1e-3, diff                                             # the same sums, two routes
+                del want, got
+                mem_k = peak_extra(lambda: gptq_amd.quant_grid_grad(x, dy, qw, bits, gs, perm=perm), dev)
+                mem_d = peak_extra(dense, dev)
+                reps = 20 if M <= 256 else 5
+                t_k, t_d = alternate(kern, dense, reps, args.warmup, args.iters)
+                flops = 2.0 * M * K * N
+                floor_c, floor_m = flops / PEAK_FLOPS, (packed_bytes + (M * K + M * N) * 2 + 2 * G * N * 4) / PEAK_BW
+                bound = "mfma" if floor_c >= floor_m else "hbm"
+                r = dict(K=K, N=N, M=M, bits=bits, groupsize=gs, perm=with_perm, grid_grad_us=t_k * 1e6, dense_us=t_d * 1e6,
+                         ratio=t_k / t_d, tflops=flops / t_k / 1e12, bound=bound, roof_share=max(floor_c, floor_m) / t_k,
+                         workspace_bytes=nb, grid_grad_peak_bytes=mem_k, dense_peak_bytes=mem_d, max_rel_diff=diff)
+                rows.append(r)
+                print(f"{K:>5}->{N:<5} {bits}b g{gs:<4}{' perm' if with_perm else '     '} M={M:<5} grid_grad {r['grid_grad_us']:9.1f} us"
+                      f"  dense {r['dense_us']:9.1f} us  ratio {r['ratio']:5.2f}  {r['tflops']:6.1f} TF/s {100 * r['roof_share']:5.1f}% of"
+                      f" {bound} roof  peak {mem_k / 2 ** 20:7.1f} MiB vs {mem_d / 2 ** 20:7.1f} MiB", flush=True)
+                del x, dy, ds, dz, db, ws
+            del qw, codes_kn
+    out = args.json or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                    "qgemm_grid_grad.json")
+    with open(out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(dev), "iters": args.iters, "warmup": args.warmup,
+                   "reps_per_graph": {"M<=256": 20, "M>256": 5}, "rows": rows}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grid-grad", action="store_true",
+                    help="the grid gradients (dscales, dzeros, dbias) against the dense x.t() @ dy route")
     ap.add_argument("--backward", action="store_true",
                     help="the transposed dequant GEMM against dequant_packed + torch.matmul")
     ap.add_argument("--iters", type=int, default=30)
@@ -222,6 +318,8 @@ def main():
         return main_perm(args)
     if args.backward:
         return main_backward(args)
+    if args.grid_grad:
+        return main_grid_grad(args)
     import gptq_amd
     from gptq_amd import _lib
     from gptq_amd.quant import pack_codes
