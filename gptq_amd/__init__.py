@@ -7,8 +7,8 @@ from .gptq import GPTQ, fasterquant_many, flush_pending  # noqa: F401
 from .modelutils import DEV, find_layers  # noqa: F401
 from .quant import (Quant2Linear, Quant3Linear, Quant4Linear, Quant8Linear, QuantGroupLinear,  # noqa: F401
                     Quantizer, frozen_grids, make_quant2, make_quant3, make_quant4, make_quant8, pack_codes,
-                    pack_grouped, quant_grid_grad, quant_matmul, quant_matmul_t, quantize, set_multi_token,
-                    trainable_grids)
+                    pack_grouped, quant_grid_grad, quant_matmul, quant_matmul_a8, quant_matmul_t, quantize,
+                    quantize_activations, set_act_bits, set_multi_token, trainable_grids)
 
 from .sequential import QuantArgs, check_wbits, packed_wbits, wbits_for  # noqa: F401
 

@@ -68,6 +68,9 @@ _SIGNATURES = {
     "gptq_quant_gemm_grid_grad": (C.c_int, [_p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
     "gptq_quant_gemm_grid_grad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "gptq_quant_gemm_grid_grad_perm_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "gptq_quant_act_rows": (C.c_int, [_p, _i, _i, _i, _i, _p, _p, _i, _p, _p]),
+    "gptq_quant_gemm_a8": (C.c_int, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _z, _p]),
+    "gptq_quant_gemm_a8_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -286,6 +286,134 @@ def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_d
     return y.reshape(outshape)
 
 
+A8_MAX_K = 65536          # 255 * 127 * K must stay below 2^31 (the int32 sums of gptq_quant_gemm_a8)
+
+
+def quantize_activations(x, perm=None):
+    """x [..., K] (fp16 / bf16) -> (xq int8 [..., K], sx fp32 [...]): one symmetric int8 grid per token row
+    (gptq_quant_act_rows).  With a = max_k |x[m][k]| in fp32,
+
+        sx[m] = a / 127 (IEEE fp32 division; 1.0 when a == 0),   xq[m][k] = clamp(rint(x[m][k] / sx[m]), -127, 127)
+
+    with a true division and round-half-even.  `perm` (int32 [K]): the act-order gather fused in, xq[m][k] is the code of
+    x[m][perm[k]] (the row maximum does not depend on the order), so the result equals the call on x[..., perm].
+    K must be a multiple of 32.  Non-finite activations (inf, nan) are outside the contract: their codes and scales are
+    unspecified."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"quantize_activations: x must be an fp16 or bf16 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() == 0:
+        raise ValueError("quantize_activations: x must have at least one dimension")
+    K = x.shape[-1]
+    if K == 0 or K % 32:
+        raise ValueError(f"quantize_activations: the last dimension must be a positive multiple of 32, got {K}")
+    if perm is not None:
+        perm = check_perm(perm, K, x, "quantize_activations")
+    _lib.require_gpu(x, "x")
+    dev = x.device
+    x2 = x.detach().reshape(-1, K)
+    M = x2.shape[0]
+    if x2.stride(-1) != 1 or (M > 1 and x2.stride(0) < K):
+        x2 = x2.contiguous()
+    xq = torch.empty((M, K), dtype=torch.int8, device=dev)
+    sx = torch.empty(M, dtype=torch.float32, device=dev)
+    if M:
+        with torch.cuda.device(dev):
+            _lib.call("gptq_quant_act_rows", _lib.ptr(x2), _lib.dtype_code(x2), max(x2.stride(0), K), M, K, _lib.ptr(perm),
+                      _lib.ptr(xq), K, _lib.ptr(sx), _lib.stream(dev))
+    return xq.reshape(x.shape), sx.reshape(x.shape[:-1])
+
+
+def quant_matmul_a8(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_dtype=None, perm=None):
+    """`quant_matmul` on int8 activations (gptq_quant_gemm_a8): an opt-in serving mode, INFERENCE ONLY.
+
+    `x` is either an fp16 / bf16 tensor [..., K], quantized inside by `quantize_activations(x, perm)`, or the pair
+    `(xq, sx)` that call returns (int8 [..., K] and fp32 [...]; already in storage order, so `perm` must be None).  The
+    other operands and their checks are those of `quant_matmul`; `out_dtype` defaults to x.dtype (fp16 for the pair).  Per
+    output and per group g of K (per-row grids: one group), with exact int32 sums on the integer-MFMA units,
+
+        I_g = sum q[k][n] xq[m][k],  X_g = sum xq[m][k],  y[m][n] = sx[m] * sum_g (s[g][n] I_g - z[g][n] X_g) + bias[n]
+
+    in fp32 with one rounding to `out_dtype`; the same call gives the same bits.  The result differs from `quant_matmul`
+    by the int8 rounding of the activations (about 2^-8 of each row's largest value per element).  K <= 65536.  There is
+    no backward: with grad enabled and an `x`, `scales`, `zeros` or `bias` that requires grad this raises ValueError."""
+    who = "quant_matmul_a8"
+    pair = isinstance(x, (tuple, list))
+    if pair:
+        if len(x) != 2 or not all(isinstance(t, torch.Tensor) for t in x):
+            raise ValueError(f"{who}: x must be a tensor or the pair (xq, sx)")
+        xq, sx = x
+        if xq.dtype != torch.int8 or sx.dtype != torch.float32:
+            raise ValueError(f"{who}: the pair must be (int8 xq, fp32 sx), got ({xq.dtype}, {sx.dtype})")
+        if xq.dim() == 0 or tuple(sx.shape) != tuple(xq.shape[:-1]):
+            raise ValueError(f"{who}: sx {tuple(sx.shape)} must have the shape of xq {tuple(xq.shape)} without its last "
+                             "dimension")
+        if perm is not None:
+            raise ValueError(f"{who}: perm belongs to the activation quantization; the pair (xq, sx) is in storage order")
+        shape, default_dtype = xq.shape, torch.float16
+    else:
+        if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"{who}: x must be fp16 or bf16 (or the pair (xq, sx)), got {getattr(x, 'dtype', type(x))}")
+        if x.dim() == 0:
+            raise ValueError(f"{who}: x must have at least one dimension")
+        shape, default_dtype = x.shape, x.dtype
+    if torch.is_grad_enabled() and ((not pair and x.requires_grad) or (pair and sx.requires_grad)
+                                    or _grids_need_grad(scales, zeros, bias)):
+        raise ValueError(f"{who}: inference only -- no backward through int8 activations (use quant_matmul, or "
+                         "torch.no_grad())")
+    if out_dtype is None:
+        out_dtype = default_dtype
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"{who}: out_dtype must be fp32, fp16 or bf16, got {out_dtype}")
+    bits, groupsize = _check_bits(bits, who), int(groupsize)
+    if qweight.dtype != torch.int32 or qweight.dim() != 2:
+        raise ValueError(f"{who}: qweight must be an int32 [K/32*bits, N] tensor")
+    K, N = shape[-1], qweight.shape[1]
+    if K == 0 or K % 32 or qweight.shape[0] != K // 32 * bits:
+        raise ValueError(f"{who}: x has {K} input features, qweight {tuple(qweight.shape)} implies "
+                         f"{qweight.shape[0] // bits * 32} (and K must be a multiple of 32)")
+    if K > A8_MAX_K:
+        raise ValueError(f"{who}: K = {K} exceeds {A8_MAX_K}, the bound that keeps the int32 sums exact")
+    if groupsize > 0:
+        if groupsize % 32 or K % groupsize:
+            raise ValueError(f"{who}: groupsize must be a multiple of 32 that divides K")
+        want = (K // groupsize, N)
+        if tuple(scales.shape) != want or tuple(zeros.shape) != want:
+            raise ValueError(f"{who}: grouped scales / zeros must be {want}")
+    elif scales.numel() != N or zeros.numel() != N:
+        raise ValueError(f"{who}: per-row scales / zeros must hold {N} values")
+    if bias is not None and bias.numel() != N:
+        raise ValueError(f"{who}: bias must hold {N} values")
+    if perm is not None and groupsize <= 0:
+        raise ValueError(f"{who}: perm (the act-order format) needs grouped grids")
+    if not pair:
+        xq, sx = quantize_activations(x, perm)               # (checks perm; needs the GPU)
+    for name, t in (("xq", xq), ("sx", sx), ("qweight", qweight), ("scales", scales), ("zeros", zeros)):
+        _lib.require_gpu(t, name)
+    if bias is not None:
+        _lib.require_gpu(bias, "bias")
+    dev = xq.device
+    outshape = list(shape[:-1]) + [N]
+    xq2 = xq.reshape(-1, K)
+    M = xq2.shape[0]
+    if xq2.stride(-1) != 1 or (M > 1 and xq2.stride(0) < K):
+        xq2 = xq2.contiguous()
+    sx1 = sx.detach().reshape(-1).contiguous()
+    y = torch.empty((M, N), dtype=out_dtype, device=dev)
+    if M == 0:
+        return y.reshape(outshape)
+    qw = qweight.contiguous()
+    s = scales.detach().to(torch.float32).contiguous()
+    z = zeros.detach().to(torch.float32).contiguous()
+    b = bias.detach().to(torch.float32).contiguous() if bias is not None else None
+    nbytes = _lib.load().gptq_quant_gemm_a8_workspace_bytes(M, K, N, bits, groupsize)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _lib.call("gptq_quant_gemm_a8", _lib.ptr(xq2), max(xq2.stride(0), K), _lib.ptr(sx1), M, _lib.ptr(qw), _lib.ptr(s),
+                  _lib.ptr(z), _lib.ptr(b), K, N, bits, groupsize, _lib.ptr(y), _lib.dtype_code(y), y.stride(0),
+                  _lib.ptr(ws), nbytes, _lib.stream(dev))
+    return y.reshape(outshape)
+
+
 def quant_matmul_t(grad, qweight, scales, zeros, bits, groupsize=-1, out_dtype=None, perm=None):
     """grad [..., N] (fp16 / bf16) times the TRANSPOSED packed weights -> [..., K] in `out_dtype` (default grad.dtype),
     through the transposed dequant GEMM of libgptq_hip.so (gptq_quant_gemm_t): the gradient of `quant_matmul` and of the
@@ -534,6 +662,7 @@ def frozen_grids(model):
 
 class _QuantLinearBase(nn.Module):
     bits = 0
+    act_bits = None    # 8: multi-token inputs outside autograd take quant_matmul_a8 (a plain attribute; set_act_bits)
 
     def _alloc(self, infeatures, outfeatures):
         self.register_buffer('zeros', torch.zeros((outfeatures, 1)))
@@ -564,6 +693,8 @@ class _QuantLinearBase(nn.Module):
         if torch.is_grad_enabled() and (x.requires_grad or _grids_need_grad(self.scales, self.zeros, self.bias)):
             return _apply_packed(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, -1, self.bias,
                                                  forward=self._forward))
+        if self.act_bits == 8 and getattr(self, 'multi_token', False) and x.shape[-1] != x.numel():
+            return quant_matmul_a8(x, self.qweight, self.scales, self.zeros, self.bits, -1, self.bias)
         return self._forward(x)
 
     def _forward(self, x):
@@ -670,6 +801,7 @@ class QuantGroupLinear(nn.Module):
     positions of the permuted column order: storage row j holds input column perm[j] on the grid of group j // groupsize,
     and an int32 buffer `perm` [in] is added ("Grouped and act-order checkpoints").
     """
+    act_bits = None    # 8: multi-token inputs outside autograd take quant_matmul_a8 (a plain attribute; set_act_bits)
 
     def __init__(self, bits, groupsize, infeatures, outfeatures, multi_token=False, act_order=False):
         super().__init__()
@@ -749,6 +881,9 @@ class QuantGroupLinear(nn.Module):
             return _apply_packed(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, self.groupsize,
                                                  self.bias, perm=self.perm if self.act_order else None,
                                                  forward=self._forward))
+        if self.act_bits == 8 and self.multi_token and x.shape[-1] != x.numel():
+            return quant_matmul_a8(x, self.qweight, self.scales, self.zeros, self.bits, self.groupsize, self.bias,
+                                   perm=self.perm if self.act_order else None)
         return self._forward(x)
 
     def _forward(self, x):
@@ -808,4 +943,20 @@ def set_multi_token(model, enabled=True):
         if isinstance(m, (_QuantLinearBase, QuantGroupLinear)):
             m.multi_token = bool(enabled)
             n += 1
+    return n
+
+
+def set_act_bits(model, bits=8):
+    """Switch every packed Linear in `model` to int8 activations (`bits=8`) or back (`bits=None`).  With `multi_token` on
+    and `act_bits == 8`, an input of several tokens that needs no gradient takes `quant_matmul_a8`; single tokens stay on
+    the mat-vec (decode is bound by the weight bytes) and any input under autograd stays on the fp16 path, so a model's
+    training-time forward and its int8 serving forward differ by the activations' int8 rounding.  `act_bits` is a plain
+    attribute: no `state_dict` key, off by default, and with it off every output is bit-identical to before.  Returns the
+    number of modules switched."""
+    if bits not in (8, None):
+        raise ValueError(f"set_act_bits: act_bits must be 8 or None, got {bits!r}")
+    n = 0
+    for m in _packed_modules(model):
+        m.act_bits = bits
+        n += 1
     return n

@@ -377,6 +377,37 @@ int gptq_quant_gemm_grid_grad(const void* x, int x_dtype, int ldx, const void* d
 size_t gptq_quant_gemm_grid_grad_workspace_bytes(int M, int K, int N, int bits, int groupsize);
 size_t gptq_quant_gemm_grid_grad_perm_workspace_bytes(int M, int K, int N, int bits, int groupsize);
 
+/* ---------------------------------------------------------------------------
+ * Packed dequant GEMM on int8 activations (opt-in serving mode, "W4A8" and its 2/3/8-bit siblings; no reference
+ * counterpart).  Two calls: quantize the activations per token row, then an integer-MFMA GEMM on the packed codes.
+ *
+ * gptq_quant_act_rows -- one grid per token row m of x [M, K] (x_dtype GPTQ_F16 or GPTQ_BF16, widened to fp32 exactly,
+ * ldx >= K):
+ *   a        = max_k |x[m][k]|                                               (fp32)
+ *   sx[m]    = a / 127.0f  (IEEE division);  1.0f when a == 0
+ *   xq[m][k] = (int8) clamp(rintf(x[m][c(k)] / sx[m]), -127, 127),  c(k) = perm ? perm[k] : k
+ *                                                                    (true division, round-half-even)
+ * xq: int8 [M, K] row-major, ldq >= K; sx: fp32 [M]; perm int32 [K], 16-byte aligned, or NULL: the act-order gather is
+ * fused here (the row maximum does not depend on the order), so the GEMM never sees perm.  K % 32 == 0.  Non-finite
+ * activations are outside the contract.
+ *
+ * gptq_quant_gemm_a8 -- for each output (m, n) and each group g of K (groupsize <= 0: one group = all of K):
+ *   I_g = sum_{k in g} q[k][n] * xq[m][k],   X_g = sum_{k in g} xq[m][k]                   (int32, exact)
+ *   y[m][n] = sx[m] * sum_g (scales[g][n] * float(I_g) - zeros[g][n] * float(X_g)) (+ bias[n])
+ * qweight / scales / zeros (= zero*scale) / bias / bits / groupsize / y as in gptq_quant_gemm.  The integer sums run on
+ * v_mfma_i32_16x16x64_i8; everything after them is fp32 (separate multiplies and adds, groups in ascending order) with
+ * one rounding to y_dtype.  K <= 65536 (255 * 127 * K must stay below 2^31); larger K is GPTQ_ERR_INVALID.  workspace: at
+ * least gptq_quant_gemm_a8_workspace_bytes(M, K, N, bits, groupsize) bytes, 4-byte aligned (0 for shapes that need none;
+ * the query needs no device): a K split at small M cuts between groups and adds its fp32 partials in chunk order, or
+ * (per-row grids) adds exact int32 partials of I and X.  No atomics: the same call gives bit-identical y.
+ * ------------------------------------------------------------------------- */
+int gptq_quant_act_rows(const void* x, int x_dtype, int ldx, int M, int K, const int32_t* perm /* nullable */, int8_t* xq,
+                        int ldq, float* sx, gptq_stream_t stream);
+int gptq_quant_gemm_a8(const int8_t* xq, int ldq, const float* sx, int M, const int32_t* qweight, const float* scales,
+                       const float* zeros, const float* bias /* nullable */, int K, int N, int bits, int groupsize, void* y,
+                       int y_dtype, int ldy, void* workspace, size_t workspace_bytes, gptq_stream_t stream);
+size_t gptq_quant_gemm_a8_workspace_bytes(int M, int K, int N, int bits, int groupsize);
+
 #ifdef __cplusplus
 }
 #endif

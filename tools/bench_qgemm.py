@@ -26,7 +26,14 @@ it replaces, in the same process: A = x.t() @ dy in fp32 (a [K, N] tensor), A ti
 group, and dy summed over the tokens (the codes are unpacked once, outside the timed region).  Reported: both times,
 their ratio, the TFLOP/s of 2 M K N over the call and its share of the roof that bounds it, and the peak device memory
 each route adds on top of its operands (torch.cuda.max_memory_allocated around one eager call).  Results go to
-profiles/qgemm_grid_grad.json (or --json)."""
+profiles/qgemm_grid_grad.json (or --json).
+
+--a8: the GEMM on int8 activations (gptq_quant_act_rows + gptq_quant_gemm_a8, the opt-in prefill path) on the same Linears
+at M = 16, 256, 2048 for 4-bit g128, 3-bit per-row and 8-bit g128, in one process beside today's gptq_quant_gemm and dense
+fp16 torch.matmul.  Five graphs are replayed in turn: the a8 call with the activation quantization included, the a8 GEMM
+alone on a pre-quantized (xq, sx), the fp16 dequant GEMM twice (two interleaved series of the same code: their medians'
+spread is the A/A noise of the comparison) and the dense product.  Also recorded, without a gate: the relative error of the
+a8 output against the fp16 path's on randn activations.  Results go to profiles/qgemm_a8.json (or --json)."""
 import argparse
 import json
 import os
@@ -298,8 +305,100 @@ def main_grid_grad(args):
                    "reps_per_graph": {"M<=256": 20, "M>256": 5}, "rows": rows}, f, indent=1)
 
 
+A8_MS = [16, 256, 2048]
+A8_GRIDS = [(4, 128), (3, -1), (8, 128)]
+
+
+def main_a8(args):
+    import gptq_amd
+    from gptq_amd import _lib
+    from gptq_amd.quant import pack_codes
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    rows = []
+    for K, N in SHAPES:
+        Wd = (torch.randn(N, K, device=dev, generator=gen) * 0.02).half()
+        for bits, gs in A8_GRIDS:
+            codes = torch.randint(0, 2 ** bits, (N, K), device=dev, generator=gen, dtype=torch.int32).to(torch.uint8)
+            qw = pack_codes(codes, bits)
+            del codes
+            ng = K // gs if gs > 0 else 1
+            s = (torch.rand(ng, N, device=dev, generator=gen) * 0.01 + 1e-3).contiguous()
+            z = (s * 2 ** (bits - 1)).contiguous()
+            if gs <= 0:
+                s, z = s[0].contiguous(), z[0].contiguous()
+            for M in (args.ms or A8_MS):
+                x = torch.randn(M, K, device=dev, generator=gen).half()
+                y8 = torch.empty(M, N, device=dev, dtype=torch.float16)
+                y8p = torch.empty(M, N, device=dev, dtype=torch.float16)
+                y16 = torch.empty(M, N, device=dev, dtype=torch.float16)
+                yd = torch.empty(M, N, device=dev, dtype=torch.float16)
+                xq = torch.empty(M, K, device=dev, dtype=torch.int8)
+                sx = torch.empty(M, device=dev)
+                nb8 = lib.gptq_quant_gemm_a8_workspace_bytes(M, K, N, bits, gs)
+                nb16 = lib.gptq_quant_gemm_workspace_bytes(M, K, N, bits, gs)
+                ws8 = torch.empty(max(nb8, 1), dtype=torch.uint8, device=dev)
+                ws16 = torch.empty(max(nb16, 1), dtype=torch.uint8, device=dev)
+                st = _lib.stream
+
+                def quant():
+                    _lib.call("gptq_quant_act_rows", x.data_ptr(), _lib.F16, K, M, K, None, xq.data_ptr(), K, sx.data_ptr(),
+                              st(dev))
+
+                def gemm8(out):
+                    _lib.call("gptq_quant_gemm_a8", xq.data_ptr(), K, sx.data_ptr(), M, qw.data_ptr(), s.data_ptr(),
+                              z.data_ptr(), None, K, N, bits, gs, out.data_ptr(), _lib.F16, N, ws8.data_ptr(), nb8, st(dev))
+
+                def full8():
+                    quant()
+                    gemm8(y8)
+
+                pre8 = lambda: gemm8(y8p)                                              # noqa: E731
+                f16 = lambda: _lib.call("gptq_quant_gemm", x.data_ptr(), _lib.F16, K, M, qw.data_ptr(), s.data_ptr(),  # noqa: E731
+                                        z.data_ptr(), None, K, N, bits, gs, y16.data_ptr(), _lib.F16, N, ws16.data_ptr(), nb16,
+                                        st(dev))
+                dense = lambda: torch.matmul(x, Wd.t(), out=yd)                        # noqa: E731
+                full8(); pre8(); f16()
+                torch.cuda.synchronize()
+                assert torch.equal(y8, gptq_amd.quant_matmul_a8(x, qw, s, z, bits, gs)) and torch.equal(y8, y8p)
+                assert torch.equal(y16, gptq_amd.quant_matmul(x, qw, s, z, bits, gs))
+                rel = float((y8.float() - y16.float()).norm() / y16.float().norm())
+                reps = 20 if M <= 256 else 5
+                graphs = [graphed(f, reps) for f in (full8, pre8, f16, f16, dense)]
+                for _ in range(args.warmup):
+                    for g in graphs:
+                        g.replay()
+                t = [[] for _ in graphs]
+                for _ in range(args.iters):                                            # the five in turn
+                    for i, g in enumerate(graphs):
+                        t[i] += timed(g, reps, 1)
+                t_full, t_pre, t_a, t_b, t_d = (statistics.median(v) for v in t)
+                t16 = 0.5 * (t_a + t_b)
+                aa = abs(t_a - t_b) / t16
+                flops = 2.0 * M * K * N
+                r = dict(K=K, N=N, M=M, bits=bits, groupsize=gs, a8_full_us=t_full * 1e6, a8_gemm_us=t_pre * 1e6,
+                         fp16_path_us=t16 * 1e6, fp16_path_series_us=[t_a * 1e6, t_b * 1e6], aa_spread=aa,
+                         dense_fp16_us=t_d * 1e6, full_over_fp16_path=t_full / t16, full_over_dense=t_full / t_d,
+                         fp16_path_over_dense=t16 / t_d, a8_gemm_tflops=flops / t_pre / 1e12,
+                         faster_than_fp16_path_beyond_aa=t_full < min(t_a, t_b) * (1 - aa), rel_err_vs_fp16_path=rel,
+                         a8_workspace_bytes=nb8)
+                rows.append(r)
+                print(f"{K:>5}->{N:<5} {bits}b g{gs:<4} M={M:<5} a8 full {r['a8_full_us']:8.1f} us  gemm {r['a8_gemm_us']:8.1f} us"
+                      f"  fp16 path {r['fp16_path_us']:8.1f} us (A/A {100 * aa:4.1f}%)  dense {r['dense_fp16_us']:8.1f} us"
+                      f"  full/fp16 {r['full_over_fp16_path']:5.2f}  full/dense {r['full_over_dense']:5.2f}"
+                      f"  {r['a8_gemm_tflops']:6.1f} TOP/s  rel err {rel:.2e}", flush=True)
+                del graphs
+    out = args.json or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "qgemm_a8.json")
+    with open(out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(dev), "iters": args.iters, "warmup": args.warmup,
+                   "reps_per_graph": {"M<=256": 20, "M>256": 5}, "rows": rows}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--a8", action="store_true",
+                    help="the GEMM on int8 activations beside the fp16 dequant GEMM and dense fp16")
     ap.add_argument("--grid-grad", action="store_true",
                     help="the grid gradients (dscales, dzeros, dbias) against the dense x.t() @ dy route")
     ap.add_argument("--backward", action="store_true",
@@ -314,6 +413,8 @@ def main():
     args = ap.parse_args()
     from gptq_amd.build import ensure_built
     ensure_built()
+    if args.a8:
+        return main_a8(args)
     if args.perm:
         return main_perm(args)
     if args.backward:
