@@ -71,6 +71,9 @@ _SIGNATURES = {
     "gptq_quant_act_rows": (C.c_int, [_p, _i, _i, _i, _i, _p, _p, _i, _p, _p]),
     "gptq_quant_gemm_a8": (C.c_int, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _z, _p]),
     "gptq_quant_gemm_a8_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "gptq_repack_rows": (C.c_int, [_p, _p, _i, _i, _i, _p, _p]),
+    "gptq_qzeros_pack": (C.c_int, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "gptq_qzeros_unpack": (C.c_int, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

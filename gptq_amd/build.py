@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libgptq_hip.so")
 DIAG_LIB = os.path.join(HERE, "libgptq_hip_diag.so")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 SOURCES = ["core.cpp", "hessian.hip", "cholesky.hip", "fasterquant.hip", "quant_super.hip", "pack.hip", "matvec.hip",
-           "qgemm.hip", "qgemm_t.hip", "qgemm_g.hip", "qgemm_a8.hip"]
+           "qgemm.hip", "qgemm_t.hip", "qgemm_g.hip", "qgemm_a8.hip", "interop.hip"]
 # -ffp-contract=off: the quantize / error-feedback chain must round exactly like the reference's
 # separate torch ops (no implicit FMA); MFMA and explicit fmaf() are unaffected.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]

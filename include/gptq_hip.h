@@ -408,6 +408,42 @@ int gptq_quant_gemm_a8(const int8_t* xq, int ldq, const float* sx, int M, const 
                        int y_dtype, int ldy, void* workspace, size_t workspace_bytes, gptq_stream_t stream);
 size_t gptq_quant_gemm_a8_workspace_bytes(int M, int K, int N, int bits, int groupsize);
 
+/* ---------------------------------------------------------------------------
+ * Checkpoints of other GPTQ tools (the qweight / qzeros / scales / g_idx layout of AutoGPTQ and its relatives; no
+ * reference counterpart).  There, for a Linear with K inputs, N outputs and G groups (K % 32 == 0, N % 32 == 0):
+ *   qweight int32 [K/32*bits, N]   the bit layout above, code rows in ORIGINAL input order
+ *   g_idx   int32 [K]              the group of every original input column
+ *   scales  fp16  [G, N]
+ *   qzeros  int32 [G, N/32*bits]   stored zero points packed ALONG N by the same rule: value v of column n at bit
+ *                                  bits*(n%32) of the stream of `bits` words starting at word (n/32)*bits;
+ *                                  v = z - zero_offset, zero_offset 1 ("gptq") or 0 ("gptq_v2"), z the integer zero point
+ *   W[n][k] = scales[g_idx[k]][n] * (code[k][n] - z[g_idx[k]][n])
+ * Here act-order models keep the code rows in permuted order plus `perm`, and the grids as fp32 scales / zero*scale.
+ *
+ * gptq_repack_rows -- code row j of qweight_out = code row row_src[j] of qweight_in (both int32 [in/32*bits, out]); 3-bit
+ * codes that straddle words move like any other.  row_src: int32 [in], a permutation of 0..in-1 (the caller validates it;
+ * an entry outside that range packs code 0 and reads nothing).  Import passes perm, export its inverse.  The two buffers
+ * must not overlap.  in % 32 == 0.
+ *
+ * gptq_qzeros_pack -- scales / zeros fp32 [G, N] (zeros = zero*scale) -> qzeros, scales16 (fp16 [G, N], round to nearest
+ * even) and *flags |= bits (int32, OR-ed with atomics: the caller zeroes it).  Per entry z = rintf(zeros / scales) (IEEE
+ * division), stored v = z - zero_offset.  Flag bits:
+ *    1  (float)z * scales != zeros: the grid is no longer an integer zero point times its scale
+ *    2  z outside [zero_offset, 2^bits - 1] (stored as 0)
+ *    4  the scale is 0, inf or nan as fp16
+ *    8  the scale is not exactly representable in fp16 (informational)
+ *   16  some z != 2^(bits-1), i.e. an asymmetric grid (informational)
+ * gptq_qzeros_unpack -- the inverse: scales = (float)scales16, zeros = (float)(v + zero_offset) * scales (one fp32
+ * rounding; v + zero_offset is NOT masked, a stored 2^bits - 1 under "gptq" gives z = 2^bits like the common kernels).
+ * Both need N % 32 == 0 and G <= 65535.
+ * ------------------------------------------------------------------------- */
+int gptq_repack_rows(const int32_t* qweight_in, const int32_t* row_src, int in_features, int out_features, int bits,
+                     int32_t* qweight_out, gptq_stream_t stream);
+int gptq_qzeros_pack(const float* scales, const float* zeros, int G, int N, int bits, int zero_offset, int32_t* qzeros,
+                     void* scales16, int32_t* flags, gptq_stream_t stream);
+int gptq_qzeros_unpack(const int32_t* qzeros, const void* scales16, int G, int N, int bits, int zero_offset, float* scales,
+                       float* zeros, gptq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
