@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .quant import PACKED_LINEAR, QuantGroupLinear, _check_bits, _QuantLinearBase, check_perm
+from .quant import PACKED_LINEAR, QuantGroupLinear, _check_bits, _packed_modules, _QuantLinearBase, check_perm
 
 CHECKPOINT_FORMATS = {"gptq": 1, "gptq_v2": 0}          # -> zero_offset: stored value = zero point - zero_offset
 FLAG_OFF_GRID, FLAG_ZERO_RANGE, FLAG_SCALE_F16, FLAG_SCALE_INEXACT, FLAG_ASYM = 1, 2, 4, 8, 16
@@ -234,10 +234,6 @@ def from_gptq_tensors(tensors, bits, group_size, checkpoint_format="gptq", multi
     return m.to(home)
 
 
-def _packed_named(model):
-    return [(name, m) for name, m in model.named_modules() if isinstance(m, (_QuantLinearBase, QuantGroupLinear))]
-
-
 def _uniform_config(packed, who):
     """(bits, group_size) shared by every packed Linear; ValueError naming two that differ."""
     if not packed:
@@ -257,7 +253,7 @@ def gptq_checkpoint_keys(model):
     """The keys `export_gptq_state_dict(model)[0]` has, without converting anything (no GPU needed): under every packed
     Linear's prefix the foreign keys replace the module's own (`bias` only where it has a non-zero entry); every other
     entry keeps its key."""
-    packed = dict(_packed_named(model))
+    packed = dict(_packed_modules(model, named=True))
     own = {f"{p}.{k}" if p else k for p in packed for k in OWN_KEYS}
     keys = [k for k in model.state_dict() if k not in own]
     for p, m in packed.items():
@@ -273,7 +269,7 @@ def export_gptq_state_dict(model, checkpoint_format="gptq", strict=False):
     share bits and group_size (ValueError naming two that do not)."""
     who = "export_gptq_state_dict"
     _zero_offset(checkpoint_format, who)
-    packed = _packed_named(model)
+    packed = _packed_modules(model, named=True)
     bits, group_size = _uniform_config(packed, who)
     own = {f"{p}.{k}" if p else k for p, _ in packed for k in OWN_KEYS}
     sd = {k: v for k, v in model.state_dict().items() if k not in own}

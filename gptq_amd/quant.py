@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import quant_cuda  # noqa: F401  (the extension-module name is part of the reference API)
+from ._packed import PACKED_BITS, _check_bits, _check_operands, _f32, _launch, _on_gpu, _rows, check_perm  # noqa: F401
 
 
 def _dev_of(t: torch.Tensor) -> torch.device:
@@ -103,16 +104,6 @@ class Quantizer(nn.Module):
         return torch.all(self.scale != 0)
 
 
-PACKED_BITS = (2, 3, 4, 8)
-
-
-def _check_bits(bits, who):
-    bits = int(bits)
-    if bits not in PACKED_BITS:
-        raise ValueError(f"{who}: bits must be 2, 3, 4 or 8, got {bits}")
-    return bits
-
-
 def _pack(weight, scales, zeros_scaled, bits):
     """[out, in] weights on the grid -> int32 [in/32*bits, out] (quant.py:158-186 / zeroShot quant.py:176-185)."""
     bits = _check_bits(bits, "_pack")
@@ -144,19 +135,6 @@ def pack_codes(codes, bits):
     return qweight
 
 
-def check_perm(perm, n_in, ref, who):
-    """The act-order permutation as the kernels take it: int32 [n_in] on `ref`'s device, contiguous and 16-byte aligned.
-    Raises ValueError before any launch."""
-    if perm.dtype != torch.int32:
-        raise ValueError(f"{who}: perm must be int32, got {perm.dtype}")
-    if perm.dim() != 1 or perm.numel() != n_in:
-        raise ValueError(f"{who}: perm must hold {n_in} entries (one per input feature), got shape {tuple(perm.shape)}")
-    if perm.device != ref.device:
-        raise ValueError(f"{who}: perm is on {perm.device}, the operands on {ref.device}")
-    p = perm.contiguous()
-    return p if p.data_ptr() % 16 == 0 else p.clone()
-
-
 def dequant_packed(qweight, scale, zero, bits, groupsize, dtype=torch.float16, perm=None):
     """int32 [in/32*bits, out] + grids [G, out] (`zero` = integer zero point) -> dense [out, in] weights,
     computed as scale * (code - zero) like the solver itself (quant.py:10).  `perm` (int32 [in]): the act-order format,
@@ -170,16 +148,9 @@ def dequant_packed(qweight, scale, zero, bits, groupsize, dtype=torch.float16, p
         perm = check_perm(perm, n_in, qweight, "dequant_packed")
     dev = _dev_of(qweight)
     W = torch.empty((n_out, n_in), dtype=dtype, device=dev)
-    s = scale.to(torch.float32).contiguous()
-    z = zero.to(torch.float32).contiguous()
-    with torch.cuda.device(dev):
-        if perm is None:
-            _lib.call("gptq_dequant_packed", _lib.ptr(qweight.contiguous()), _lib.ptr(s), _lib.ptr(z), n_out, n_in,
-                      int(bits), int(groupsize), _lib.ptr(W), _lib.dtype_code(W), W.stride(0), _lib.stream(dev))
-        else:
-            _lib.call("gptq_dequant_packed_perm", _lib.ptr(qweight.contiguous()), _lib.ptr(s), _lib.ptr(z), _lib.ptr(perm),
-                      n_out, n_in, int(bits), int(groupsize), _lib.ptr(W), _lib.dtype_code(W), W.stride(0),
-                      _lib.stream(dev))
+    symbol, extra = ("gptq_dequant_packed", ()) if perm is None else ("gptq_dequant_packed_perm", (perm,))
+    _launch(symbol, dev, qweight.contiguous(), _f32(scale), _f32(zero), *extra, n_out, n_in, bits, int(groupsize),
+            W, _lib.dtype_code(W), W.stride(0))
     return W
 
 
@@ -229,61 +200,17 @@ def quant_matmul(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, out_d
         out_dtype = x.dtype
     if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(f"quant_matmul: out_dtype must be fp32, fp16 or bf16, got {out_dtype}")
-    bits, groupsize = int(bits), int(groupsize)
-    bits = _check_bits(bits, "quant_matmul")
-    if qweight.dtype != torch.int32 or qweight.dim() != 2:
-        raise ValueError("quant_matmul: qweight must be an int32 [K/32*bits, N] tensor")
-    K, N = x.shape[-1], qweight.shape[1]
-    if K % 32 or qweight.shape[0] != K // 32 * bits:
-        raise ValueError(f"quant_matmul: x has {K} input features, qweight {tuple(qweight.shape)} implies "
-                         f"{qweight.shape[0] // bits * 32} (and K must be a multiple of 32)")
-    if groupsize > 0:
-        if groupsize % 32 or K % groupsize:
-            raise ValueError("quant_matmul: groupsize must be a multiple of 32 that divides K")
-        want = (K // groupsize, N)
-        if tuple(scales.shape) != want or tuple(zeros.shape) != want:
-            raise ValueError(f"quant_matmul: grouped scales / zeros must be {want}")
-    elif scales.numel() != N or zeros.numel() != N:
-        raise ValueError(f"quant_matmul: per-row scales / zeros must hold {N} values")
-    if bias is not None and bias.numel() != N:
-        raise ValueError(f"quant_matmul: bias must hold {N} values")
-    if perm is not None:
-        if groupsize <= 0:
-            raise ValueError("quant_matmul: perm (the act-order format) needs grouped grids")
-        perm = check_perm(perm, K, x, "quant_matmul")
-    for name, t in (("x", x), ("qweight", qweight), ("scales", scales), ("zeros", zeros)):
-        _lib.require_gpu(t, name)
-    if bias is not None:
-        _lib.require_gpu(bias, "bias")
-    dev = x.device
-    outshape = list(x.shape[:-1]) + [N]
-    x2 = x.reshape(-1, K)
-    if x2.stride(-1) != 1:
-        x2 = x2.contiguous()
+    K, N, bits, groupsize, perm = _check_operands("quant_matmul", qweight, bits, groupsize, scales, zeros, bias, perm,
+                                                  ref=x, K=x.shape[-1])
+    _on_gpu(("x", x), ("qweight", qweight), ("scales", scales), ("zeros", zeros), ("bias", bias))
+    x2, ldx = _rows(x, K)
     M = x2.shape[0]
-    y = torch.empty((M, N), dtype=out_dtype, device=dev)
-    if M == 0:
-        return y.reshape(outshape)
-    qw = qweight.contiguous()
-    s = scales.to(torch.float32).contiguous()
-    z = zeros.to(torch.float32).contiguous()
-    b = bias.to(torch.float32).contiguous() if bias is not None else None
-    lib = _lib.load()
-    if perm is None:
-        nbytes = lib.gptq_quant_gemm_workspace_bytes(M, K, N, bits, groupsize)
-    else:
-        nbytes = lib.gptq_quant_gemm_perm_workspace_bytes(M, K, N, bits, groupsize)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    with torch.cuda.device(dev):
-        if perm is None:
-            _lib.call("gptq_quant_gemm", _lib.ptr(x2), _lib.dtype_code(x2), x2.stride(0), M, _lib.ptr(qw), _lib.ptr(s),
-                      _lib.ptr(z), _lib.ptr(b), K, N, bits, groupsize, _lib.ptr(y), _lib.dtype_code(y), y.stride(0),
-                      _lib.ptr(ws), nbytes, _lib.stream(dev))
-        else:
-            _lib.call("gptq_quant_gemm_perm", _lib.ptr(x2), _lib.dtype_code(x2), x2.stride(0), M, _lib.ptr(qw),
-                      _lib.ptr(s), _lib.ptr(z), _lib.ptr(perm), _lib.ptr(b), K, N, bits, groupsize, _lib.ptr(y),
-                      _lib.dtype_code(y), y.stride(0), _lib.ptr(ws), nbytes, _lib.stream(dev))
-    return y.reshape(outshape)
+    y = torch.empty((M, N), dtype=out_dtype, device=x.device)
+    if M:
+        symbol, extra = ("gptq_quant_gemm", ()) if perm is None else ("gptq_quant_gemm_perm", (perm,))
+        _launch(symbol, x.device, x2, _lib.dtype_code(x2), ldx, M, qweight.contiguous(), _f32(scales), _f32(zeros), *extra,
+                _f32(bias), K, N, bits, groupsize, y, _lib.dtype_code(y), y.stride(0), ws_dims=(M, K, N, bits, groupsize))
+    return y.reshape(list(x.shape[:-1]) + [N])
 
 
 A8_MAX_K = 65536          # 255 * 127 * K must stay below 2^31 (the int32 sums of gptq_quant_gemm_a8)
@@ -308,18 +235,18 @@ def quantize_activations(x, perm=None):
         raise ValueError(f"quantize_activations: the last dimension must be a positive multiple of 32, got {K}")
     if perm is not None:
         perm = check_perm(perm, K, x, "quantize_activations")
+    return _quant_act_rows(x, K, perm)
+
+
+def _quant_act_rows(x, K, perm):
+    """`quantize_activations` behind its checks."""
     _lib.require_gpu(x, "x")
-    dev = x.device
-    x2 = x.detach().reshape(-1, K)
+    x2, ldx = _rows(x.detach(), K)
     M = x2.shape[0]
-    if x2.stride(-1) != 1 or (M > 1 and x2.stride(0) < K):
-        x2 = x2.contiguous()
-    xq = torch.empty((M, K), dtype=torch.int8, device=dev)
-    sx = torch.empty(M, dtype=torch.float32, device=dev)
+    xq = torch.empty((M, K), dtype=torch.int8, device=x.device)
+    sx = torch.empty(M, dtype=torch.float32, device=x.device)
     if M:
-        with torch.cuda.device(dev):
-            _lib.call("gptq_quant_act_rows", _lib.ptr(x2), _lib.dtype_code(x2), max(x2.stride(0), K), M, K, _lib.ptr(perm),
-                      _lib.ptr(xq), K, _lib.ptr(sx), _lib.stream(dev))
+        _launch("gptq_quant_act_rows", x.device, x2, _lib.dtype_code(x2), ldx, M, K, perm, xq, K, sx)
     return xq.reshape(x.shape), sx.reshape(x.shape[:-1])
 
 
@@ -364,54 +291,19 @@ def quant_matmul_a8(x, qweight, scales, zeros, bits, groupsize=-1, bias=None, ou
         out_dtype = default_dtype
     if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(f"{who}: out_dtype must be fp32, fp16 or bf16, got {out_dtype}")
-    bits, groupsize = _check_bits(bits, who), int(groupsize)
-    if qweight.dtype != torch.int32 or qweight.dim() != 2:
-        raise ValueError(f"{who}: qweight must be an int32 [K/32*bits, N] tensor")
-    K, N = shape[-1], qweight.shape[1]
-    if K == 0 or K % 32 or qweight.shape[0] != K // 32 * bits:
-        raise ValueError(f"{who}: x has {K} input features, qweight {tuple(qweight.shape)} implies "
-                         f"{qweight.shape[0] // bits * 32} (and K must be a multiple of 32)")
-    if K > A8_MAX_K:
-        raise ValueError(f"{who}: K = {K} exceeds {A8_MAX_K}, the bound that keeps the int32 sums exact")
-    if groupsize > 0:
-        if groupsize % 32 or K % groupsize:
-            raise ValueError(f"{who}: groupsize must be a multiple of 32 that divides K")
-        want = (K // groupsize, N)
-        if tuple(scales.shape) != want or tuple(zeros.shape) != want:
-            raise ValueError(f"{who}: grouped scales / zeros must be {want}")
-    elif scales.numel() != N or zeros.numel() != N:
-        raise ValueError(f"{who}: per-row scales / zeros must hold {N} values")
-    if bias is not None and bias.numel() != N:
-        raise ValueError(f"{who}: bias must hold {N} values")
-    if perm is not None and groupsize <= 0:
-        raise ValueError(f"{who}: perm (the act-order format) needs grouped grids")
+    K, N, bits, groupsize, perm = _check_operands(who, qweight, bits, groupsize, scales, zeros, bias, perm, ref=x,
+                                                  K=shape[-1], max_k=A8_MAX_K)
     if not pair:
-        xq, sx = quantize_activations(x, perm)               # (checks perm; needs the GPU)
-    for name, t in (("xq", xq), ("sx", sx), ("qweight", qweight), ("scales", scales), ("zeros", zeros)):
-        _lib.require_gpu(t, name)
-    if bias is not None:
-        _lib.require_gpu(bias, "bias")
-    dev = xq.device
-    outshape = list(shape[:-1]) + [N]
-    xq2 = xq.reshape(-1, K)
+        xq, sx = _quant_act_rows(x, K, perm)                  # (the first step that needs the GPU)
+    _on_gpu(("xq", xq), ("sx", sx), ("qweight", qweight), ("scales", scales), ("zeros", zeros), ("bias", bias))
+    xq2, ldx = _rows(xq, K)
     M = xq2.shape[0]
-    if xq2.stride(-1) != 1 or (M > 1 and xq2.stride(0) < K):
-        xq2 = xq2.contiguous()
-    sx1 = sx.detach().reshape(-1).contiguous()
-    y = torch.empty((M, N), dtype=out_dtype, device=dev)
-    if M == 0:
-        return y.reshape(outshape)
-    qw = qweight.contiguous()
-    s = scales.detach().to(torch.float32).contiguous()
-    z = zeros.detach().to(torch.float32).contiguous()
-    b = bias.detach().to(torch.float32).contiguous() if bias is not None else None
-    nbytes = _lib.load().gptq_quant_gemm_a8_workspace_bytes(M, K, N, bits, groupsize)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    with torch.cuda.device(dev):
-        _lib.call("gptq_quant_gemm_a8", _lib.ptr(xq2), max(xq2.stride(0), K), _lib.ptr(sx1), M, _lib.ptr(qw), _lib.ptr(s),
-                  _lib.ptr(z), _lib.ptr(b), K, N, bits, groupsize, _lib.ptr(y), _lib.dtype_code(y), y.stride(0),
-                  _lib.ptr(ws), nbytes, _lib.stream(dev))
-    return y.reshape(outshape)
+    y = torch.empty((M, N), dtype=out_dtype, device=xq.device)
+    if M:
+        _launch("gptq_quant_gemm_a8", xq.device, xq2, ldx, sx.reshape(-1).contiguous(), M, qweight.contiguous(),
+                _f32(scales), _f32(zeros), _f32(bias), K, N, bits, groupsize, y, _lib.dtype_code(y), y.stride(0),
+                ws_dims=(M, K, N, bits, groupsize))
+    return y.reshape(list(shape[:-1]) + [N])
 
 
 def quant_matmul_t(grad, qweight, scales, zeros, bits, groupsize=-1, out_dtype=None, perm=None):
@@ -428,51 +320,17 @@ def quant_matmul_t(grad, qweight, scales, zeros, bits, groupsize=-1, out_dtype=N
         out_dtype = grad.dtype
     if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(f"quant_matmul_t: out_dtype must be fp32, fp16 or bf16, got {out_dtype}")
-    bits, groupsize = int(bits), int(groupsize)
-    bits = _check_bits(bits, "quant_matmul_t")
-    if qweight.dtype != torch.int32 or qweight.dim() != 2:
-        raise ValueError("quant_matmul_t: qweight must be an int32 [K/32*bits, N] tensor")
-    N = qweight.shape[1]
-    if qweight.shape[0] % bits or qweight.shape[0] == 0:
-        raise ValueError(f"quant_matmul_t: qweight {tuple(qweight.shape)} is no [K/32*{bits}, N] buffer "
-                         "(K must be a multiple of 32)")
-    K = qweight.shape[0] // bits * 32
-    if grad.shape[-1] != N:
-        raise ValueError(f"quant_matmul_t: grad has {grad.shape[-1]} output features, qweight {tuple(qweight.shape)} "
-                         f"implies {N}")
-    if groupsize > 0:
-        if groupsize % 32 or K % groupsize:
-            raise ValueError("quant_matmul_t: groupsize must be a multiple of 32 that divides K")
-        want = (K // groupsize, N)
-        if tuple(scales.shape) != want or tuple(zeros.shape) != want:
-            raise ValueError(f"quant_matmul_t: grouped scales / zeros must be {want}")
-    elif scales.numel() != N or zeros.numel() != N:
-        raise ValueError(f"quant_matmul_t: per-row scales / zeros must hold {N} values")
-    if perm is not None:
-        if groupsize <= 0:
-            raise ValueError("quant_matmul_t: perm (the act-order format) needs grouped grids")
-        perm = check_perm(perm, K, grad, "quant_matmul_t")
-    for name, t in (("grad", grad), ("qweight", qweight), ("scales", scales), ("zeros", zeros)):
-        _lib.require_gpu(t, name)
-    dev = grad.device
-    outshape = list(grad.shape[:-1]) + [K]
-    g2 = grad.reshape(-1, N)
-    if g2.stride(-1) != 1 or (g2.shape[0] > 1 and g2.stride(0) < N):   # (expanded grads, e.g. of sum(), have stride 0)
-        g2 = g2.contiguous()
+    K, N, bits, groupsize, perm = _check_operands("quant_matmul_t", qweight, bits, groupsize, scales, zeros, perm=perm,
+                                                  ref=grad, N=grad.shape[-1])
+    _on_gpu(("grad", grad), ("qweight", qweight), ("scales", scales), ("zeros", zeros))
+    g2, ldg = _rows(grad, N)
     M = g2.shape[0]
-    dx = torch.empty((M, K), dtype=out_dtype, device=dev)
-    if M == 0:
-        return dx.reshape(outshape)
-    qw = qweight.contiguous()
-    s = scales.to(torch.float32).contiguous()
-    z = zeros.to(torch.float32).contiguous()
-    nbytes = _lib.load().gptq_quant_gemm_t_workspace_bytes(M, K, N, bits, groupsize)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    with torch.cuda.device(dev):
-        _lib.call("gptq_quant_gemm_t", _lib.ptr(g2), _lib.dtype_code(g2), max(g2.stride(0), N), M, _lib.ptr(qw),
-                  _lib.ptr(s), _lib.ptr(z), _lib.ptr(perm), K, N, bits, groupsize, _lib.ptr(dx), _lib.dtype_code(dx),
-                  dx.stride(0), _lib.ptr(ws), nbytes, _lib.stream(dev))
-    return dx.reshape(outshape)
+    dx = torch.empty((M, K), dtype=out_dtype, device=grad.device)
+    if M:
+        _launch("gptq_quant_gemm_t", grad.device, g2, _lib.dtype_code(g2), ldg, M, qweight.contiguous(), _f32(scales),
+                _f32(zeros), perm, K, N, bits, groupsize, dx, _lib.dtype_code(dx), dx.stride(0),
+                ws_dims=(M, K, N, bits, groupsize))
+    return dx.reshape(list(grad.shape[:-1]) + [K])
 
 
 def quant_grid_grad(x, grad, qweight, bits, groupsize=-1, perm=None, bias=True):
@@ -489,51 +347,24 @@ def quant_grid_grad(x, grad, qweight, bits, groupsize=-1, perm=None, bias=True):
         raise ValueError(f"quant_grid_grad: x must be fp16 or bf16, got {x.dtype}")
     if grad.dtype != x.dtype:
         raise ValueError(f"quant_grid_grad: grad must have x's dtype {x.dtype}, got {grad.dtype}")
-    bits, groupsize = int(bits), int(groupsize)
-    bits = _check_bits(bits, "quant_grid_grad")
-    if qweight.dtype != torch.int32 or qweight.dim() != 2:
-        raise ValueError("quant_grid_grad: qweight must be an int32 [K/32*bits, N] tensor")
-    K, N = x.shape[-1], qweight.shape[1]
-    if K == 0 or K % 32 or qweight.shape[0] != K // 32 * bits:
-        raise ValueError(f"quant_grid_grad: x has {K} input features, qweight {tuple(qweight.shape)} implies "
-                         f"{qweight.shape[0] // bits * 32} (and K must be a multiple of 32)")
-    if grad.shape[-1] != N:
-        raise ValueError(f"quant_grid_grad: grad has {grad.shape[-1]} output features, qweight {tuple(qweight.shape)} "
-                         f"implies {N}")
+    K, N, bits, groupsize, perm = _check_operands("quant_grid_grad", qweight, bits, groupsize, perm=perm, ref=x,
+                                                  K=x.shape[-1], N=grad.shape[-1])
     if x.numel() // K != grad.numel() // N:
         raise ValueError(f"quant_grid_grad: x {tuple(x.shape)} and grad {tuple(grad.shape)} hold different numbers of tokens")
-    if groupsize > 0 and (groupsize % 32 or K % groupsize):
-        raise ValueError("quant_grid_grad: groupsize must be a multiple of 32 that divides K")
-    if perm is not None:
-        if groupsize <= 0:
-            raise ValueError("quant_grid_grad: perm (the act-order format) needs grouped grids")
-        perm = check_perm(perm, K, x, "quant_grid_grad")
-    for name, t in (("x", x), ("grad", grad), ("qweight", qweight)):
-        _lib.require_gpu(t, name)
+    _on_gpu(("x", x), ("grad", grad), ("qweight", qweight))
     dev = x.device
-    x2, g2 = x.reshape(-1, K), grad.reshape(-1, N)
+    (x2, ldx), (g2, ldg) = _rows(x, K), _rows(grad, N)
     M = x2.shape[0]
-    if x2.stride(-1) != 1 or (M > 1 and x2.stride(0) < K):
-        x2 = x2.contiguous()
-    if g2.stride(-1) != 1 or (M > 1 and g2.stride(0) < N):   # (expanded grads, e.g. of sum(), have stride 0)
-        g2 = g2.contiguous()
-    G = K // groupsize if groupsize > 0 else 1
-    shape = (G, N) if groupsize > 0 else (N,)
+    shape = (K // groupsize, N) if groupsize > 0 else (N,)
     if M == 0:
         return (torch.zeros(shape, device=dev), torch.zeros(shape, device=dev),
                 torch.zeros(N, device=dev) if bias else None)
     ds = torch.empty(shape, dtype=torch.float32, device=dev)
     dz = torch.empty(shape, dtype=torch.float32, device=dev)
     db = torch.empty(N, dtype=torch.float32, device=dev) if bias else None
-    qw = qweight.contiguous()
-    lib = _lib.load()
-    query = lib.gptq_quant_gemm_grid_grad_workspace_bytes if perm is None else lib.gptq_quant_gemm_grid_grad_perm_workspace_bytes
-    nbytes = query(M, K, N, bits, groupsize)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    with torch.cuda.device(dev):
-        _lib.call("gptq_quant_gemm_grid_grad", _lib.ptr(x2), _lib.dtype_code(x2), max(x2.stride(0), K), _lib.ptr(g2),
-                  max(g2.stride(0), N), M, _lib.ptr(qw), _lib.ptr(perm), K, N, bits, groupsize, _lib.ptr(ds), _lib.ptr(dz),
-                  _lib.ptr(db), _lib.ptr(ws), nbytes, _lib.stream(dev))
+    _launch("gptq_quant_gemm_grid_grad", dev, x2, _lib.dtype_code(x2), ldx, g2, ldg, M, qweight.contiguous(), perm,
+            K, N, bits, groupsize, ds, dz, db, ws_dims=(M, K, N, bits, groupsize),
+            ws_symbol=None if perm is None else "gptq_quant_gemm_grid_grad_perm")
     return ds, dz, db
 
 
@@ -560,28 +391,39 @@ class _GemmForward:
             lambda x: quant_matmul(x, qweight, scales, zeros, bits, groupsize, bias, out_dtype, perm))
 
 
+def _packed_forward(ctx, x, op):
+    """The forward of both Functions: the path taken without autograd, run without grad (so the same bits)."""
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"backward through packed Linears needs fp16/bf16 activations, got {x.dtype}")
+    ctx.op = op
+    ctx.x_dtype = x.dtype
+    with torch.no_grad():
+        return op.forward(x.detach())
+
+
+def _grad_input(ctx, grad):
+    """The start of both backwards: (grad in x's dtype, which the weights round to -- it differs under an fp32
+    `out_dtype`; dx = `quant_matmul_t` of it, or None where x needs no gradient)."""
+    op = ctx.op
+    if grad.dtype != ctx.x_dtype:
+        grad = grad.to(ctx.x_dtype)
+    if not ctx.needs_input_grad[0]:
+        return grad, None
+    return grad, quant_matmul_t(grad, op.qweight, op.scales.detach(), op.zeros.detach(), op.bits, op.groupsize,
+                                ctx.x_dtype, op.perm)
+
+
 class _PackedLinearFn(torch.autograd.Function):
     """y = packed(x) with a gradient for x only (no grid tensor requires grad; see `_PackedGridFn`).  Forward: exactly the path taken
     without autograd -- the dequant GEMM for several tokens, the mat-vec for one.  Backward: `quant_matmul_t`."""
 
     @staticmethod
     def forward(ctx, x, op):
-        if x.dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError(f"backward through packed Linears needs fp16/bf16 activations, got {x.dtype}")
-        ctx.op = op
-        ctx.x_dtype = x.dtype
-        with torch.no_grad():
-            return op.forward(x.detach())
+        return _packed_forward(ctx, x, op)
 
     @staticmethod
     def backward(ctx, grad):
-        op = ctx.op
-        if grad.dtype != ctx.x_dtype:                        # (an fp32 `out_dtype`): the weights round to x's type
-            grad = grad.to(ctx.x_dtype)
-        per_row = op.groupsize <= 0
-        dx = quant_matmul_t(grad, op.qweight, op.scales.reshape(-1) if per_row else op.scales,
-                            op.zeros.reshape(-1) if per_row else op.zeros, op.bits, op.groupsize, ctx.x_dtype, op.perm)
-        return dx, None
+        return _grad_input(ctx, grad)[1], None
 
 
 class _PackedGridFn(torch.autograd.Function):
@@ -592,26 +434,15 @@ class _PackedGridFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, scales, zeros, bias, op):
-        if x.dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError(f"backward through packed Linears needs fp16/bf16 activations, got {x.dtype}")
-        ctx.op = op
-        ctx.x_dtype = x.dtype
         if any(ctx.needs_input_grad[1:4]):
             ctx.save_for_backward(x)
-        with torch.no_grad():
-            return op.forward(x.detach())
+        return _packed_forward(ctx, x, op)
 
     @staticmethod
     def backward(ctx, grad):
         op = ctx.op
-        if grad.dtype != ctx.x_dtype:
-            grad = grad.to(ctx.x_dtype)
-        per_row = op.groupsize <= 0
-        dx = ds = dz = db = None
-        if ctx.needs_input_grad[0]:
-            dx = quant_matmul_t(grad, op.qweight, op.scales.detach().reshape(-1) if per_row else op.scales.detach(),
-                                op.zeros.detach().reshape(-1) if per_row else op.zeros.detach(), op.bits, op.groupsize,
-                                ctx.x_dtype, op.perm)
+        grad, dx = _grad_input(ctx, grad)
+        ds = dz = db = None
         if any(ctx.needs_input_grad[1:4]):
             x, = ctx.saved_tensors
             gs, gz, gb = quant_grid_grad(x, grad, op.qweight, op.bits, op.groupsize, op.perm,
@@ -628,8 +459,10 @@ class _PackedGridFn(torch.autograd.Function):
 GRID_NAMES = ("scales", "zeros", "bias")
 
 
-def _packed_modules(model):
-    return [m for m in model.modules() if isinstance(m, (_QuantLinearBase, QuantGroupLinear))]
+def _packed_modules(model, named=False):
+    """Every packed Linear of `model` (per-row and grouped modules alike); with `named`, as (name, module) pairs."""
+    found = [(name, m) for name, m in model.named_modules() if isinstance(m, _PackedLinear)]
+    return found if named else [m for _, m in found]
 
 
 def trainable_grids(model, scales=True, zeros=True, bias=True):
@@ -660,15 +493,56 @@ def frozen_grids(model):
     return n
 
 
-class _QuantLinearBase(nn.Module):
-    bits = 0
+class _PackedLinear(nn.Module):
+    """What the five packed Linears share: the route of `forward` (autograd, int8 activations, `_forward`) and the
+    single-token / multi-token split of `_forward`.  A subclass supplies `_operands`, `_vec` and `_matvec`."""
     act_bits = None    # 8: multi-token inputs outside autograd take quant_matmul_a8 (a plain attribute; set_act_bits)
+    multi_token = False
 
-    def _alloc(self, infeatures, outfeatures):
-        self.register_buffer('zeros', torch.zeros((outfeatures, 1)))
-        self.register_buffer('scales', torch.zeros((outfeatures, 1)))
-        self.register_buffer('bias', torch.zeros(outfeatures))
-        self.register_buffer('qweight', torch.zeros((infeatures // 32 * self.bits, outfeatures), dtype=torch.int))
+    @staticmethod
+    def _staging_device(home):
+        """Where `pack` runs for a Linear on `home`: there if it is a GPU, else on the current one."""
+        if home.type == 'cuda':
+            return home
+        if torch.cuda.is_available():
+            return torch.device('cuda', torch.cuda.current_device())
+        raise _lib.GptqHipError("packing needs an MI355X device; gptq_amd has no CPU path")
+
+    def forward(self, x):
+        if torch.is_grad_enabled() and (x.requires_grad or _grids_need_grad(self.scales, self.zeros, self.bias)):
+            return _apply_packed(x, _GemmForward(*self._operands(), forward=self._forward))
+        if self.act_bits == 8 and self.multi_token and x.shape[-1] != x.numel():
+            return quant_matmul_a8(x, *self._operands())
+        return self._forward(x)
+
+    def _forward(self, x):
+        if x.shape[-1] == x.numel():
+            y = self.bias.clone().float()
+            self._matvec(self._vec(x), y)
+            return y.to(x.dtype).reshape(list(x.shape[:-1]) + [self.bias.numel()])
+        if self.multi_token:
+            return quant_matmul(x, *self._operands())
+        raise ValueError('Only supports a single token currently.')
+
+
+class _QuantLinearBase(_PackedLinear):
+    """Packed Linear with one (scale, zero) per output row.  The constructor accepts either (infeatures, outfeatures)
+    like Quant3Linear or the reference's (linear, scales, zeros) form (zeroShot/models/quant.py:172)."""
+    bits = 0
+    faster = False
+
+    def __init__(self, infeatures, outfeatures=None, zeros=None, faster=False, multi_token=False):
+        super().__init__()
+        self.faster = faster
+        self.multi_token = multi_token   # inputs of several tokens -> quant_matmul (a plain attribute: no state_dict key)
+        linear = infeatures if isinstance(infeatures, nn.Module) else None
+        n_in, n_out = (linear.in_features, linear.out_features) if linear is not None else (infeatures, outfeatures)
+        self.register_buffer('zeros', torch.zeros((n_out, 1)))
+        self.register_buffer('scales', torch.zeros((n_out, 1)))
+        self.register_buffer('bias', torch.zeros(n_out))
+        self.register_buffer('qweight', torch.zeros((n_in // 32 * self.bits, n_out), dtype=torch.int))
+        if linear is not None:
+            self.pack(linear, outfeatures, zeros)
 
     def pack(self, linear, scales, zeros):
         """Same contract as Quant3Linear.pack (quant.py:152-187): `zeros` is the integer zero point.
@@ -677,10 +551,7 @@ class _QuantLinearBase(nn.Module):
         staged on the GPU, packed there and the buffers return to the source device.
         """
         home = linear.weight.device
-        dev = home if home.type == 'cuda' else torch.device('cuda', torch.cuda.current_device()) \
-            if torch.cuda.is_available() else None
-        if dev is None:
-            raise _lib.GptqHipError("packing needs an MI355X device; gptq_amd has no CPU path")
+        dev = self._staging_device(home)
         scales = scales.to(dev)
         self.zeros = (zeros.to(dev) * scales).to(home)
         self.scales = scales.clone().to(home)
@@ -689,30 +560,11 @@ class _QuantLinearBase(nn.Module):
         qweight = _pack(linear.weight.data.to(dev), scales, self.zeros.to(dev), self.bits)
         self.qweight = qweight.to(home)
 
-    def forward(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or _grids_need_grad(self.scales, self.zeros, self.bias)):
-            return _apply_packed(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, -1, self.bias,
-                                                 forward=self._forward))
-        if self.act_bits == 8 and getattr(self, 'multi_token', False) and x.shape[-1] != x.numel():
-            return quant_matmul_a8(x, self.qweight, self.scales, self.zeros, self.bits, -1, self.bias)
-        return self._forward(x)
+    def _operands(self):
+        return self.qweight, self.scales, self.zeros, self.bits, -1, self.bias
 
-    def _forward(self, x):
-        if x.shape[-1] == x.numel():
-            outshape = list(x.shape)
-            y = self.bias.clone().float()
-            outshape[-1] = self.bias.numel()
-            dtype = x.dtype
-            if getattr(self, 'faster', False):
-                x = x.half()
-            else:
-                x = x.float()
-            self._matvec(x, y)
-            y = y.to(dtype)
-            return y.reshape(outshape)
-        if getattr(self, 'multi_token', False):
-            return quant_matmul(x, self.qweight, self.scales, self.zeros, self.bits, -1, self.bias)
-        raise ValueError('Only supports a single token currently.')
+    def _vec(self, x):
+        return x.half() if self.faster else x.float()
 
 
 class Quant3Linear(_QuantLinearBase):
@@ -722,10 +574,7 @@ class Quant3Linear(_QuantLinearBase):
     bits = 3
 
     def __init__(self, infeatures, outfeatures, faster=False, multi_token=False):
-        super().__init__()
-        self._alloc(infeatures, outfeatures)
-        self.faster = faster
-        self.multi_token = multi_token   # inputs of several tokens -> quant_matmul (a plain attribute: no state_dict key)
+        super().__init__(infeatures, outfeatures, faster=faster, multi_token=multi_token)
 
     def _matvec(self, x, y):
         if self.faster:
@@ -743,54 +592,29 @@ class Quant4Linear(_QuantLinearBase):
     """
     bits = 4
 
-    def __init__(self, infeatures, outfeatures=None, zeros=None, faster=False, multi_token=False):
-        super().__init__()
-        self.faster = faster
-        self.multi_token = multi_token
-        if isinstance(infeatures, nn.Module):
-            linear, scales = infeatures, outfeatures
-            self._alloc(linear.in_features, linear.out_features)
-            self.pack(linear, scales, zeros)
-        else:
-            self._alloc(infeatures, outfeatures)
-
     def _matvec(self, x, y):
         quant_cuda.vecquant4matmul(x, self.qweight, y, self.scales, self.zeros)
 
 
-class _QuantPow2Linear(_QuantLinearBase):
-    """Per-row packed Linear of a width that divides 32 (2 / 8 bits): the 4-bit module's rule with 16 / 4 codes per
-    word, qweight int32 [in/32*bits, out].  Same constructor forms and buffers as Quant4Linear."""
-
-    def __init__(self, infeatures, outfeatures=None, zeros=None, faster=False, multi_token=False):
-        super().__init__()
-        self.faster = faster
-        self.multi_token = multi_token
-        if isinstance(infeatures, nn.Module):
-            linear, scales = infeatures, outfeatures
-            self._alloc(linear.in_features, linear.out_features)
-            self.pack(linear, scales, zeros)
-        else:
-            self._alloc(infeatures, outfeatures)
-
-
-class Quant2Linear(_QuantPow2Linear):
-    """2-bit packed Linear: code i of a column in word i // 16 at bit 2 * (i % 16)."""
+class Quant2Linear(_QuantLinearBase):
+    """2-bit packed Linear: code i of a column in word i // 16 at bit 2 * (i % 16).  The 4-bit module's rule with 16
+    codes per word; same constructor forms and buffers as Quant4Linear."""
     bits = 2
 
     def _matvec(self, x, y):
         quant_cuda.vecquant2matmul(x, self.qweight, y, self.scales, self.zeros)
 
 
-class Quant8Linear(_QuantPow2Linear):
-    """8-bit packed Linear: code i of a column in byte i % 4 of word i // 4."""
+class Quant8Linear(_QuantLinearBase):
+    """8-bit packed Linear: code i of a column in byte i % 4 of word i // 4.  The 4-bit module's rule with 4 codes per
+    word; same constructor forms and buffers as Quant4Linear."""
     bits = 8
 
     def _matvec(self, x, y):
         quant_cuda.vecquant8matmul(x, self.qweight, y, self.scales, self.zeros)
 
 
-class QuantGroupLinear(nn.Module):
+class QuantGroupLinear(_PackedLinear):
     """Packed Linear with one (scale, zero) per `groupsize` input columns.
 
     The reference cannot pack grouped models (Quant3Linear keeps per-row scalars, quant.py:144-145, and
@@ -801,7 +625,6 @@ class QuantGroupLinear(nn.Module):
     positions of the permuted column order: storage row j holds input column perm[j] on the grid of group j // groupsize,
     and an int32 buffer `perm` [in] is added ("Grouped and act-order checkpoints").
     """
-    act_bits = None    # 8: multi-token inputs outside autograd take quant_matmul_a8 (a plain attribute; set_act_bits)
 
     def __init__(self, bits, groupsize, infeatures, outfeatures, multi_token=False, act_order=False):
         super().__init__()
@@ -847,10 +670,7 @@ class QuantGroupLinear(nn.Module):
         if (perm is not None) != self.act_order:
             raise ValueError("QuantGroupLinear.pack: perm is needed exactly for act_order=True modules")
         home = linear.weight.device
-        dev = home if home.type == 'cuda' else torch.device('cuda', torch.cuda.current_device()) \
-            if torch.cuda.is_available() else None
-        if dev is None:
-            raise _lib.GptqHipError("packing needs an MI355X device; gptq_amd has no CPU path")
+        dev = self._staging_device(home)
         gs = group_scale.to(device=dev, dtype=torch.float32)
         scales = gs.t().contiguous()
         zeros = (group_zero.to(device=dev, dtype=torch.float32) * gs).t().contiguous()
@@ -876,31 +696,16 @@ class QuantGroupLinear(nn.Module):
         g[self.perm.long()] = grp
         return g
 
-    def forward(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or _grids_need_grad(self.scales, self.zeros, self.bias)):
-            return _apply_packed(x, _GemmForward(self.qweight, self.scales, self.zeros, self.bits, self.groupsize,
-                                                 self.bias, perm=self.perm if self.act_order else None,
-                                                 forward=self._forward))
-        if self.act_bits == 8 and self.multi_token and x.shape[-1] != x.numel():
-            return quant_matmul_a8(x, self.qweight, self.scales, self.zeros, self.bits, self.groupsize, self.bias,
-                                   perm=self.perm if self.act_order else None)
-        return self._forward(x)
+    def _operands(self):
+        return (self.qweight, self.scales, self.zeros, self.bits, self.groupsize, self.bias, None,
+                self.perm if self.act_order else None)
 
-    def _forward(self, x):
-        perm = self.perm if self.act_order else None
-        if x.shape[-1] == x.numel():
-            outshape = list(x.shape)
-            y = self.bias.clone().float()
-            outshape[-1] = self.bias.numel()
-            dtype = x.dtype
-            xv = x if x.dtype in (torch.float16, torch.float32) else x.float()
-            quant_cuda.vecquant_matmul_grouped(xv.reshape(-1), self.qweight, y, self.scales, self.zeros,
-                                               self.bits, self.groupsize, perm=perm)
-            return y.to(dtype).reshape(outshape)
-        if self.multi_token:
-            return quant_matmul(x, self.qweight, self.scales, self.zeros, self.bits, self.groupsize, self.bias,
-                                perm=perm)
-        raise ValueError('Only supports a single token currently.')
+    def _vec(self, x):
+        return x if x.dtype in (torch.float16, torch.float32) else x.float()
+
+    def _matvec(self, x, y):
+        quant_cuda.vecquant_matmul_grouped(x, self.qweight, y, self.scales, self.zeros, self.bits, self.groupsize,
+                                           perm=self.perm if self.act_order else None)
 
 
 def make_quant3(module, names, name='', faster=False, multi_token=False):
@@ -939,10 +744,9 @@ def set_multi_token(model, enabled=True):
     """Switch the multi-token forward (`quant_matmul`) of every packed Linear in `model` on or off, e.g. after
     loading a checkpoint into a skeleton built without it.  Returns the number of modules switched."""
     n = 0
-    for m in model.modules():
-        if isinstance(m, (_QuantLinearBase, QuantGroupLinear)):
-            m.multi_token = bool(enabled)
-            n += 1
+    for m in _packed_modules(model):
+        m.multi_token = bool(enabled)
+        n += 1
     return n
 
 

@@ -614,8 +614,8 @@ def make_packed_skeleton(model, names, bits, faster=False, multi_token=False, gr
 def packed_wbits(model) -> Dict[str, int]:
     """{name: bits} of every packed Linear of `model` (per-row and grouped modules alike): with it the skeleton of a
     mixed-width checkpoint is rebuilt as `make_packed_skeleton(fresh, list(w), bits=w)`."""
-    from .quant import QuantGroupLinear, _QuantLinearBase
-    return {name: int(m.bits) for name, m in model.named_modules() if isinstance(m, (_QuantLinearBase, QuantGroupLinear))}
+    from .quant import _packed_modules
+    return {name: int(m.bits) for name, m in _packed_modules(model, named=True)}
 
 
 @torch.no_grad()
